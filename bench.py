@@ -11,7 +11,10 @@ state each, 8 tile-sharded GPUs run it as one launch of 1024 frames = 51 GB per 
 followed by the frame-end gather of every rank's fp32 accumulation tiles to rank 0 (RCCL over
 xGMI via torch.distributed, backend "nccl") and the un-permute into the full frame on rank 0.
 
-    python bench.py [--gpus 1] [--steps 10] [--warmup 2]
+    python bench.py [--gpus 1] [--steps 10] [--warmup 2]    (the headline figure only)
+    python bench.py --full ...            (plus the CPU baseline, one-frame calls, visit counts, roofline)
+    python bench.py --dump-outputs DIR    (the last timed step's assembled frame: DIR/frame.npy, finite,
+                                           and DIR/frame_nonfinite.npy, where it was NaN or inf)
     python bench.py --gpus N ...          (spawns N rank processes itself, one per GPU)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
     python bench.py --dry-run --gpus 2    (CPU: launcher, frame plan and gloo gather only)
@@ -77,11 +80,19 @@ def parse_args(argv=None):
                          "DESIGN §5 round 5; N = 1 unchanged)")
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the CPU "
+                         "baseline, the one-frame calls (ms_per_frame_single, ms_single_frame_latency), the "
+                         "standalone wf_trace probe and the visit-count frame of the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step returned: DIR/frame.npy, the assembled fp32 "
+                         "frame (H, W, 3) with non-finite channels as 0, DIR/frame_nonfinite.npy, which of them "
+                         "were NaN / +inf / -inf, and DIR/counts.npy, float64 [rays, samples] of the timed steps")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="bounded CPU-baseline sample: oracle frames until this wall time (0 disables)")
+                    help="(--full) bounded CPU-baseline sample: oracle frames until this wall time (0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--single-frames", type=int, default=64,
-                    help="frames rendered one per rt_render call after the timed region (ms_per_frame_single)")
+                    help="(--full) frames rendered one per rt_render call after the timed region (ms_per_frame_single)")
     ap.add_argument("--pipeline", type=int, default=2,
                     help="render calls in flight together (rt_set_pipeline; 1: off): the one-frame calls of "
                          "ms_per_frame_single (and the steps with --pipeline-steps)")
@@ -100,6 +111,8 @@ def parse_args(argv=None):
     ap.add_argument("--fail-rank", type=int, default=-1,
                     help="(with --dry-run) this rank exits with status 3 before the rendezvous (launcher test)")
     a = ap.parse_args(argv)
+    if a.dump_outputs and a.no_gather:
+        ap.error("--dump-outputs writes the assembled frame: not with --no-gather")
     if a.tile <= 0:
         a.tile = 16 if a.gpus > 1 else 32
     return a
@@ -449,6 +462,42 @@ def dry_run(args, rank: int, world: int) -> int:
     return 0 if (total_px == W * H and ok) else 1
 
 
+# ------------------------------------------------------------------------------ outputs
+DUMP_MAX_BYTES = 60 * 1000 * 1000  # all files of one --dump-outputs together (below 64 MB)
+
+
+def dump_outputs(out_dir: Path, frame: np.ndarray, rays: float, samples: float) -> None:
+    """--dump-outputs: the assembled fp32 frame (H, W, 3) as arrays of finite numbers.
+
+    The reference's estimator now and then returns NaN (a division by a zero pdf, the normalised
+    zero vector of a total internal reflection: SURVEY R14, tests/test_furnace_media.py) and the
+    progressive blend keeps such a pixel NaN, so the frame a caller receives is not all finite; the
+    GPU frame equals the oracle's in those pixels too.  Written here:
+      frame.npy            float32, the frame with every non-finite channel set to 0
+      frame_nonfinite.npy  float32, same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf
+      counts.npy           float64 [rays, samples] of the timed steps
+    Together the first two hold the frame exactly.  A frame too large for DUMP_MAX_BYTES is written
+    as a fixed sample of its pixels (seed 0, ascending order): both arrays become (n, 3) and
+    frame_pixels.npy (float64) holds the sampled pixels' indices y * W + x."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    h, w, _ = frame.shape
+    px = frame.reshape(h * w, 3)
+    n_max = DUMP_MAX_BYTES // (2 * 12 + 8)  # per pixel: two fp32 rows and one fp64 index
+    if h * w * 2 * 12 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, n_max, replace=False))
+        px = px[idx]
+        np.save(out_dir / "frame_pixels.npy", idx.astype(np.float64))
+    else:
+        px = px.reshape(h, w, 3)
+    code = np.zeros(px.shape, np.float32)
+    code[np.isnan(px)] = 1.0
+    code[np.isposinf(px)] = 2.0
+    code[np.isneginf(px)] = 3.0
+    np.save(out_dir / "frame.npy", np.where(code == 0, px, np.float32(0)).astype(np.float32))
+    np.save(out_dir / "frame_nonfinite.npy", code)
+    np.save(out_dir / "counts.npy", np.array([rays, samples], np.float64))
+
+
 # ------------------------------------------------------------------------------ bench
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else argv
@@ -600,11 +649,16 @@ def main(argv=None) -> int:
                   "rank_ms": [round(x[0], 3) for x in rank_rows],  # each rank's timed wall time per step
                   "rank_max_over_mean": round(max(x[0] for x in rank_rows) / (sum(x[0] for x in rank_rows) / len(rank_rows)), 4)}
 
-    # standalone wf_trace launches for the roofline (outside the timed region): the same frame-group
-    # workload as one timed launch (frames per group = F / (batches x 2)), run as ONE group
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: the assembled frame (the running mean over every
+        # frame rendered so far) and the device's ray / sample counts of the timed steps
+        dump_outputs(Path(args.dump_outputs), frame.cpu().numpy().reshape(H, W, 3), rays, samples)
+
+    # --full: standalone wf_trace launches for the roofline (outside the timed region): the same
+    # frame-group workload as one timed launch (frames per group = F / (batches x 2)), run as ONE group
     # (RT_FLAG_SERIAL), so no other kernel shares the CUs; HIP events on the launch stream
     probe = None
-    if st["trace_launches"]:
+    if args.full and st["trace_launches"]:
         from rtamd.renderer import RT_FLAG_SERIAL
         # (rt_stats.launches counts the batches a render call is split into; two frame groups each)
         per_group = max(1, -(-F * steps // (2 * max(1, st["launches"]))))
@@ -619,11 +673,11 @@ def main(argv=None) -> int:
         torch.cuda.synchronize()
         frame_sha = hashlib.sha256(frame.cpu().numpy().tobytes()).hexdigest()
 
-    # the reference's usage pattern (main.cpp:165-200): one frame per draw, outside the timed
+    # --full: the reference's usage pattern (main.cpp:165-200): one frame per draw, outside the timed
     # region; throughput of back-to-back single-frame calls and the latency of a synchronised one
     base = (warm + steps) * F
     single = {}
-    if n_single > 0:
+    if args.full and n_single > 0:
         # back-to-back one-frame calls, one call in flight at a time and then with frames in flight
         # across calls (rt_set_pipeline: the GL driver's own frame queue; results unchanged)
         for depth in (args.pipeline, 1) if args.pipeline > 1 else (1,):
@@ -648,11 +702,13 @@ def main(argv=None) -> int:
             lat.append(time.perf_counter() - t2)
         single["ms_single_frame_latency"] = round(float(np.median(lat)) * 1e3, 3)
 
-    # own-traversal visit counts (one extra frame, outside the timed region; tools/summarize_profile.py
-    # drops the launches from this frame on)
-    r.reset_stats()
-    r.render(cf.frame_params(W, H, flags=RT_FLAG_COUNT_VISITS), ro[-1:])
-    vis = r.stats()
+    # --full: own-traversal visit counts (one extra frame, outside the timed region;
+    # tools/summarize_profile.py drops the launches from this frame on)
+    vis = None
+    if args.full:
+        r.reset_stats()
+        r.render(cf.frame_params(W, H, flags=RT_FLAG_COUNT_VISITS), ro[-1:])
+        vis = r.stats()
 
     if rank != 0:
         if dist:
@@ -702,17 +758,18 @@ def main(argv=None) -> int:
         out["frame_sha256"] = frame_sha
     if args.rehearse:
         out["rehearsal"] = "all ranks on one GPU, gloo collectives (not a scaling measurement)"
-    if vis["rays"]:
+    if vis and vis["rays"]:
         out["own_traversal_per_ray"] = {"internal": round(vis["internal_pops"] / vis["rays"], 2),
                                         "leaf": round(vis["leaf_pops"] / vis["rays"], 2),
                                         "tri": round(vis["tri_tests"] / vis["rays"], 2)}
 
-    # CPU baseline (rank 0, N = 1 only) and the §8(d) per-ray figure from its counters
-    cnt = None
-    if world == 1 and args.cpu_seconds > 0:
-        out["cpu_baseline"], cnt = cpu_baseline(sd, env, W, H, fp, args.cpu_seconds, args.cpu_threads)
-    prof = load_profile(args.config, W, H, F, path_slots)
-    out["roofline"] = roofline(st, vis, cnt, prof, probe, steps)
+    # --full: CPU baseline (rank 0, N = 1 only) and the §8(d) per-ray figure from its counters; the roofline
+    if args.full:
+        cnt = None
+        if world == 1 and args.cpu_seconds > 0:
+            out["cpu_baseline"], cnt = cpu_baseline(sd, env, W, H, fp, args.cpu_seconds, args.cpu_threads)
+        prof = load_profile(args.config, W, H, F, path_slots)
+        out["roofline"] = roofline(st, vis, cnt, prof, probe, steps)
     print(json.dumps(out), flush=True)
     if dist:
         dist.barrier()

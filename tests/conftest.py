@@ -1,5 +1,4 @@
 """Shared pytest setup: import paths, the `gpu` marker, scene/oracle fixtures."""
-import os
 import sys
 from pathlib import Path
 
@@ -14,13 +13,6 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (HIP device); run with -m gpu")
-
-
-REFERENCE = Path(os.environ.get("RT_REFERENCE_DIR", "/root/reference"))
-
-
-def have_reference() -> bool:
-    return (REFERENCE / "src" / "shaders" / "fragment_shader_ray_tracing.glsl").exists()
 
 
 @pytest.fixture(scope="session")

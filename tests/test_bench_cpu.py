@@ -186,6 +186,47 @@ def test_cpu_baseline_records_the_host():
     assert "cpu_model" in h
 
 
+def test_bench_plain_run_is_the_default():
+    """--full (CPU baseline, one-frame calls, probe and visit-count frames, roofline) is off unless
+    asked for; --dump-outputs names a directory and needs the assembled frame."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    assert bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--dump-outputs", "d", "--no-gather"])
+
+
+def test_dump_outputs_are_finite_and_hold_the_frame(tmp_path, monkeypatch):
+    """The frame keeps the NaN pixels of the reference's estimator; the dump writes finite arrays:
+    the frame with 0 there and a code array saying what was there.  A frame above the size budget
+    is written as the same seeded pixel sample every time."""
+    import bench
+    rng = np.random.default_rng(3)
+    f = rng.uniform(0, 4, (9, 16, 3)).astype(np.float32)
+    f[2, 3, 1], f[2, 3, 2], f[8, 15, 0], f[0, 0, 0] = np.nan, np.inf, -np.inf, np.nan
+    bench.dump_outputs(tmp_path / "a", f, 7.0, 3.0)
+    fr, code = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_nonfinite.npy")
+    assert fr.dtype == code.dtype == np.float32 and fr.shape == code.shape == f.shape
+    assert np.isfinite(fr).all() and code.sum() == 1 + 2 + 3 + 1
+    assert (code[2, 3, 1], code[2, 3, 2], code[8, 15, 0], code[0, 0, 0]) == (1, 2, 3, 1)
+    assert np.array_equal(fr[code == 0], f[code == 0]) and not fr[code != 0].any()
+    assert list(np.load(tmp_path / "a" / "counts.npy")) == [7.0, 3.0]
+    assert not (tmp_path / "a" / "frame_pixels.npy").exists()
+    # over the budget: n pixels, the same ones in every run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 32 * 40)
+    bench.dump_outputs(tmp_path / "b", f, 7.0, 3.0)
+    bench.dump_outputs(tmp_path / "c", f, 7.0, 3.0)
+    idx = np.load(tmp_path / "b" / "frame_pixels.npy")
+    assert idx.dtype == np.float64 and len(idx) == 40 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_pixels.npy"))
+    fb, cb = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "b" / "frame_nonfinite.npy")
+    assert fb.shape == cb.shape == (40, 3)
+    assert np.array_equal(fb, fr.reshape(-1, 3)[idx.astype(int)]) and np.array_equal(cb, code.reshape(-1, 3)[idx.astype(int)])
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= 32 * 40 + 16 + 4 * 128  # + counts + the .npy headers
+
+
 def test_bench_tile_default_follows_the_rank_count():
     """Round 5: 32-px rank tiles at N = 1, 16-px tiles at N > 1 (the cost-balanced map of smaller
     tiles evens 8 ranks out better); an explicit --tile wins."""

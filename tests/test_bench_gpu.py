@@ -38,6 +38,43 @@ def test_multi_rank_bench_frame_equals_one_rank(n, extra):
     assert one["collective"]["world"] == 1 and one["collective"]["backend"] is None
 
 
+FULL_ONLY = ("roofline", "cpu_baseline", "own_traversal_per_ray", "ms_per_frame_single", "ms_single_frame_latency")
+
+
+def test_plain_bench_prints_the_headline_and_dumps_its_frame(tmp_path):
+    """A plain run times its steps and nothing else; --dump-outputs writes the frame the last timed
+    step assembled (the one --frame-sha hashes) and the counts behind rays_per_sample."""
+    import hashlib
+
+    import numpy as np
+    d = _bench("--gpus", "1", "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+    assert not [k for k in FULL_ONLY if k in d]
+    frame = np.load(tmp_path / "out" / "frame.npy")
+    code = np.load(tmp_path / "out" / "frame_nonfinite.npy")
+    assert frame.dtype == code.dtype == np.float32 and frame.shape == code.shape == (160, 256, 3)
+    assert np.isfinite(frame).all() and frame.max() > 0 and np.isin(code, (0, 1, 2, 3)).all()
+    # the two arrays hold the frame (a NaN's payload bits aside, so the hash is compared when this
+    # small render has no NaN pixel: it has none)
+    whole = frame.copy()
+    for c, v in ((2, np.inf), (3, -np.inf)):
+        whole[code == c] = v
+    assert not frame[code != 0].any() and not (code == 1).any()
+    assert hashlib.sha256(whole.tobytes()).hexdigest() == d["frame_sha256"]
+    rays, samples = np.load(tmp_path / "out" / "counts.npy")
+    assert samples == 256 * 160 * 4 and round(rays / samples, 4) == d["rays_per_sample"]
+
+
+def test_full_bench_adds_the_roofline_and_the_one_frame_calls():
+    plain = _bench("--gpus", "1")
+    full = _bench("--gpus", "1", "--full", "--single-frames", "2")
+    assert full["frame_sha256"] == plain["frame_sha256"] and full["rays_per_sample"] == plain["rays_per_sample"]
+    assert full["roofline"]["kernel"] == "wf_trace" and "standalone" in full["roofline"]["avg_launch_ms_regime"]
+    assert full["own_traversal_per_ray"]["tri"] > 0
+    assert full["ms_per_frame_single"] > 0 and full["ms_single_frame_latency"] > 0
+    assert "cpu_baseline" not in full  # COMMON: --cpu-seconds 0
+
+
 def test_eight_rank_bench_at_full_size_frame_equals_one_rank():
     """The driver's largest configuration: 8 ranks of 1920x1080 tiles, cost-balanced map."""
     full = ["--width", "1920", "--height", "1080", "--frames-per-step", "2"]

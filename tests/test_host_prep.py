@@ -6,6 +6,7 @@ own sources (tests/golden/hdr_ref.json, and live against oracle/_ref when presen
 """
 import hashlib
 import json
+import lzma
 import subprocess
 import tempfile
 from pathlib import Path
@@ -13,7 +14,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, have_reference
+from conftest import ROOT
 from rtamd import configs as cf
 from rtamd import scene_lib as sl
 
@@ -116,19 +117,27 @@ def test_floor_quad_triangulation():
     assert np.array_equal(tris[1], [[-10, 0, 10], [10, 0, -10], [-10, 0, -10]])
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference checkout absent")
+def _obj_file(name, tmp_path):
+    """The reference's OBJ text of a mesh, kept under tests/golden/obj (the largest one xz-packed)."""
+    p = GOLD / "obj" / f"{name}.obj"
+    if p.exists():
+        return str(p)
+    out = tmp_path / f"{name}.obj"
+    out.write_bytes(lzma.decompress((GOLD / "obj" / f"{name}.obj.xz").read_bytes()))
+    return str(out)
+
+
 @pytest.mark.parametrize("name", ["floor", "bunny_4000", "loong_100000"])
-def test_assets_equal_obj_parse(name):
-    raw = sl.parse_obj_raw(str(REFERENCE / "resources" / "objects" / f"{name}.obj"), 0)
+def test_assets_equal_obj_parse(name, tmp_path):
+    raw = sl.parse_obj_raw(_obj_file(name, tmp_path), 0)
     asset = cf.load_raw_mesh(name)
     assert np.array_equal(raw.positions, asset.positions)
     assert np.array_equal(raw.pos_index, asset.pos_index)
     assert np.array_equal(raw.face_sizes, asset.face_sizes)
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference checkout absent")
-def test_assimp_parse_mode_differs_only_in_last_ulps():
-    path = str(REFERENCE / "resources" / "objects" / "bunny_4000.obj")
+def test_assimp_parse_mode_differs_only_in_last_ulps(tmp_path):
+    path = _obj_file("bunny_4000", tmp_path)
     a = sl.parse_obj_raw(path, 0).positions
     b = sl.parse_obj_raw(path, 1).positions
     ulps = np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))

@@ -16,7 +16,7 @@
 #   rank=<spec> ...         N = 8 rank shares on one GPU (tools/rank_sim.py); spec: VAR=v,VAR=v or "-"
 #   passes=<cfg>:<frames>[:VAR=v;VAR=v][:count]  per-pass times (or visit counts) of one frame group
 #                           (dev library)
-#   bench[=<bench.py args>] the driver's bench command (default args: --gpus 1 --steps 20 --warmup 5)
+#   bench[=<bench.py args>] the driver's bench command with --full (default args: --gpus 1 --steps 20 --warmup 5)
 #   configs                 bench lines of C2, C4, C5 (256-frame steps)
 #   evidence[=<tag>]        round evidence: tests, rocprofv3 trace + PMC summary, bench, interactive
 #                           (tools/round_gpu.sh)
@@ -26,6 +26,7 @@ set -o pipefail
 export TMPDIR=/tmp
 TAG=${1:?usage: gpu_run.sh <tag> <step> ...}; shift
 O=gpurun_out/$TAG; mkdir -p $O
+export RT_OUT_DIR=$(dirname $O)  # tools/round_gpu.sh and tools/profile_configs.sh write beside the tags
 E=$PWD/opengl-ray-tracing-framework_amd/lib/exp
 ROUNDS=${ROUNDS:-3}
 
@@ -74,11 +75,11 @@ for step in "$@"; do
         python3 -u tools/pass_counts.py --config $cfg --frames $fr --max-paths $((fr * 1920 * 1080)) ${pcount:+--count} > $L 2>&1 || fail $step $? $L
       grep -a "\] group\|pass" $L | head -30 ;;
     bench)
-      timeout -k 10 600 python3 bench.py ${arg:---gpus 1 --steps 20 --warmup 5} > $O/bench.json 2> $L || fail $step $? $L
+      timeout -k 10 600 python3 bench.py --full ${arg:---gpus 1 --steps 20 --warmup 5} > $O/bench.json 2> $L || fail $step $? $L
       python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print(d['value'], d['ms_per_frame'], d.get('ms_single_frame_latency'), d.get('ms_per_frame_single'), d['roofline']['frac'])" $O/bench.json ;;
     configs)
       for c in C2 C4 C5; do
-        timeout -k 10 300 python3 bench.py --config $c --frames-per-step 256 --steps 3 --warmup 1 --cpu-seconds 0 > $O/bench_$c.json 2> $L || fail $step $? $L
+        timeout -k 10 300 python3 bench.py --full --config $c --frames-per-step 256 --steps 3 --warmup 1 --cpu-seconds 0 > $O/bench_$c.json 2> $L || fail $step $? $L
         python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print('$c', d['value'], d['ms_per_frame'], d.get('ms_single_frame_latency'), d['rays_per_sample'], d['own_traversal_per_ray'])" $O/bench_$c.json
       done ;;
     evidence)
@@ -87,7 +88,8 @@ for step in "$@"; do
     profile_configs)
       bash tools/profile_configs.sh ${arg:-r06} > $L 2>&1 || fail $step $? $L
       grep -E "^C[45] " $L
-      timeout -k 10 300 python3 bench.py --config C2 --frames-per-step 256 --steps 3 --warmup 1 > gpurun_out/profiles/${arg:-r06}_bench_C2.json 2>> $L || fail $step $? $L
+      P=$(dirname $O)/profiles  # (where tools/profile_configs.sh left its summaries)
+      timeout -k 10 300 python3 bench.py --full --config C2 --frames-per-step 256 --steps 3 --warmup 1 > $P/${arg:-r06}_bench_C2.json 2>> $L || fail $step $? $L
       python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print('C2', d['value'], d['ms_per_frame'], d.get('ms_single_frame_latency'), d.get('ms_per_frame_single'))" gpurun_out/profiles/${arg:-r06}_bench_C2.json ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac

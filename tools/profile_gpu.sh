@@ -7,7 +7,7 @@
 # memory-copy domains.
 set -euo pipefail
 OUT=${1:-gpurun_out/prof}
-ARGS=${BENCH_ARGS:-"--steps 3 --warmup 1 --cpu-seconds 0 --single-frames 0"}
+ARGS=${BENCH_ARGS:-"--full --steps 3 --warmup 1 --cpu-seconds 0 --single-frames 0"}  # (--full: the probe and visit-count frames)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {  # name, rocprofv3 options...
