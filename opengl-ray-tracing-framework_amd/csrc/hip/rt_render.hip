@@ -742,6 +742,35 @@ void launch_trace(rt_ctx* c, bool count, dim3 grid, const rtd::WFParams& WP, hip
   else launch_trace_t<false>(c, grid, WP, st, small);
 }
 
+// The shade of one pass over `slots` path slots.  fused: one frame per path-state set, the blend
+// inside the shade (WFParams::fuse_blend); bulk: groups above finish_slots, RT_SH_SUB_BULK paths
+// per thread and block-iteration; cam: the camera pass of a bulk group with >= 64 frames
+// (camera-hit records); plain: everything else
+enum class ShadeKind { plain, bulk, cam, fused };
+template <bool BSDF>
+void launch_shade_t(ShadeKind kind, dim3 grid, hipStream_t st, const rtd::WFParams& WP) {
+  if (kind == ShadeKind::fused) hipLaunchKernelGGL((rtd::wf_shade<BSDF, true>), grid, dim3(256), 0, st, WP);
+  else if (kind == ShadeKind::cam) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_CAM, true>), grid, dim3(256), 0, st, WP);
+  else if (kind == ShadeKind::bulk) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_BULK>), grid, dim3(256), 0, st, WP);
+  else hipLaunchKernelGGL((rtd::wf_shade<BSDF, false>), grid, dim3(256), 0, st, WP);
+}
+void launch_shade(bool bsdf, ShadeKind kind, unsigned int slots, hipStream_t st, const rtd::WFParams& WP) {
+  const unsigned int sub = kind == ShadeKind::cam    ? (unsigned)rtd::SH_SUB_CAM
+                           : kind == ShadeKind::bulk ? (unsigned)rtd::SH_SUB_BULK
+                                                     : (unsigned)rtd::SH_SUB;
+  const dim3 grid(std::max(1u, std::min<unsigned int>(4096u, (slots + 256u * sub - 1) / (256u * sub))));
+  if (bsdf) launch_shade_t<true>(kind, grid, st, WP);
+  else launch_shade_t<false>(kind, grid, st, WP);
+}
+
+// wf_finish: one lane per remaining path, trace + shade until the path ends
+void launch_finish(rt_ctx* c, bool bsdf, dim3 grid, hipStream_t st, const rtd::WFParams& WP) {
+  if (bsdf && c->wide) hipLaunchKernelGGL((rtd::wf_finish<true, true>), grid, dim3(256), c->trace_lds, st, WP);
+  else if (bsdf) hipLaunchKernelGGL((rtd::wf_finish<true, false>), grid, dim3(256), c->trace_lds, st, WP);
+  else if (c->wide) hipLaunchKernelGGL((rtd::wf_finish<false, true>), grid, dim3(256), c->trace_lds, st, WP);
+  else hipLaunchKernelGGL((rtd::wf_finish<false, false>), grid, dim3(256), c->trace_lds, st, WP);
+}
+
 hipEvent_t take_event(rt_ctx* c) {
   if (!c->event_pool.empty()) {
     hipEvent_t e = c->event_pool.back();
@@ -752,6 +781,11 @@ hipEvent_t take_event(rt_ctx* c) {
   if (hipEventCreate(&e) != hipSuccess) return nullptr;
   return e;
 }
+#define TAKE_EVENT(ctx, ev)                                                                      \
+  do {                                                                                           \
+    (ev) = take_event(ctx);                                                                      \
+    if (!(ev)) return fail((ctx), RT_ERR_HIP, "hipEventCreate failed");                          \
+  } while (0)
 
 // Timing events of launches not yet folded into kernel_ms / trace_ms: a front end that never
 // calls rt_synchronize (it waits on its own stream or events) would otherwise grow these lists
@@ -833,7 +867,7 @@ int fold_trace_events(rt_ctx* c, size_t cap) {
 constexpr size_t kMaxPendingEvents = 4096;
 
 // Frames in flight per launch = path-state budget / pixels of this rank.  The state grows on
-// demand in rt_render_async, so interactive 1-frame use stays small.  More frames per launch
+// demand in reserve_path_state, so interactive 1-frame use stays small.  More frames per launch
 // amortise the per-pass latency floor of the few longest rays (C3 1080p: 16 frames 1.07, 64
 // frames 0.94 ms/frame; 161 vs 80 frames +1.8%, all 512 of a bench step at once +2.2%).
 void update_frames_cap(rt_ctx* c, size_t nv) {
@@ -1351,93 +1385,143 @@ int rt_clear_accum(rt_ctx* c) {
   return RT_OK;
 }
 
-int rt_render_async(rt_ctx* c, const rt_frame_params* fp, const float* rand_origin, int32_t n_frames) {
-  if (!c || !fp || n_frames < 0 || (n_frames && !rand_origin)) return RT_ERR_ARG;
-  if (!c->scene_set || !c->env_set || !c->frame_set) return fail(c, RT_ERR_STATE, "set_scene, set_env and resize first");
-  if ((fp->flags & RT_FLAG_MEGAKERNEL) && !fp->enable_bsdf)
-    return fail(c, RT_ERR_ARG, "BRDF mode (enable_bsdf = 0) runs on the wavefront path only");
-  HIPCHK(c, hipSetDevice(c->device));
-  // main.cpp:175: LoopNum++ while below maxIterations; frames at the cap copy history (R12).
-  int n_trace_pre = 0;
-  for (int k = 0, ln = c->loop_num; k < n_frames; k++) {
+}  // extern "C"
+
+// The steps of rt_render_async, in the order they run.
+namespace {
+
+#ifdef RT_DEV
+#include "rt_dev_report.h"
+#endif
+
+// What one rt_render_async call decided, on its stack, handed from step to step.
+struct RenderCall {
+  struct Frame { int loop_num, ro_bits; };
+  std::vector<Frame> frames;       // the traced frames' (loopNum, randOrigin bits), in call order
+  int n_traced = 0;                // frames.size()
+  int loop_end = 0;                // rt_ctx::loop_num after the call
+  int pipe_sets = 0;
+  bool pipe = false, serial = false;
+  int pset = 0;                    // pipelined: path-state set, camera table, overflow column, stream aux[1 + pset]
+  hipStream_t ps = nullptr;        // the stream that runs this call
+  hipEvent_t e_entry = nullptr;    // pipelined: the caller's stream at entry (the blend waits for it)
+  rt_ctx::LightTable* LT = nullptr;
+  const int* d_loop = nullptr;     // the frame table on the device (stage_frame_table)
+  const float* d_ro = nullptr;
+  float2* d_sobol = nullptr;
+  float2* d_blendw = nullptr;
+};
+
+// main.cpp:175: LoopNum++ while below maxIterations; frames at the cap copy history (R12).  Listed
+// before anything can fail; stage_frame_table moves rt_ctx::loop_num, so a call that fails before
+// it leaves loop_num untouched.
+void list_traced_frames(const rt_ctx* c, const rt_frame_params* fp, const float* rand_origin, int n_frames, RenderCall& call) {
+  int ln = c->loop_num;
+  for (int k = 0; k < n_frames; k++) {
     if (fp->max_iterations == -1 || ln < fp->max_iterations) ln++;
-    if (fp->max_iterations == -1 || ln < fp->max_iterations) n_trace_pre++;
+    if (!(fp->max_iterations == -1 || ln < fp->max_iterations)) continue;
+    RenderCall::Frame f{ln, 0};
+    memcpy(&f.ro_bits, &rand_origin[k], 4);
+    call.frames.push_back(f);
   }
-  // a pipelined call (rt_set_pipeline): see rt_ctx::pipe_depth.  One-frame calls, and calls of
-  // one batch (at most frames_cap frames) whose whole path state fits in each set.
-  static const bool pix_ok = !knob("RT_PIX_SPLIT") || atoi(knob("RT_PIX_SPLIT")) != 0;
-  const int pipe_sets = std::min(c->pipe_depth, c->n_groups);
+  call.n_traced = (int)call.frames.size();
+  call.loop_end = ln;
+}
+
+// a batch of fewer frames than groups splits by pixels (RT_PIX_SPLIT=0, dev: it stays one group)
+bool pix_split_ok() {
+  static const bool ok = !knob("RT_PIX_SPLIT") || atoi(knob("RT_PIX_SPLIT")) != 0;
+  return ok;
+}
+
+// a pipelined call (rt_set_pipeline): see rt_ctx::pipe_depth.  One-frame calls, and calls of
+// one batch (at most frames_cap frames) whose whole path state fits in each set.
+void admit_pipeline(rt_ctx* c, const rt_frame_params* fp, RenderCall& call) {
+  const int n = call.n_traced;
   const size_t nv = std::max<size_t>(1, (size_t)c->n_valid);
-  const bool serial = (fp->flags & RT_FLAG_SERIAL) != 0 && !(fp->flags & RT_FLAG_MEGAKERNEL);
-  bool pipe = pipe_sets >= 2 && !(fp->flags & RT_FLAG_MEGAKERNEL) && !serial && n_trace_pre > 0 &&
+  call.pipe_sets = std::min(c->pipe_depth, c->n_groups);
+  call.serial = (fp->flags & RT_FLAG_SERIAL) != 0 && !(fp->flags & RT_FLAG_MEGAKERNEL);
+  call.pipe = call.pipe_sets >= 2 && !(fp->flags & RT_FLAG_MEGAKERNEL) && !call.serial && n > 0 &&
               c->n_valid >= 64 * c->n_groups && !c->tile_cost_on &&
-              (n_trace_pre < c->n_groups ||
-               (n_trace_pre <= c->frames_cap && (size_t)n_trace_pre * nv < c->pipe_nomem_slots));
-  if (pipe && n_trace_pre < c->n_groups && pix_ok) {
+              (n < c->n_groups || (n <= c->frames_cap && (size_t)n * nv < c->pipe_nomem_slots));
+  if (call.pipe && n < c->n_groups && pix_split_ok()) {
     // a one-frame call with no call in flight has nothing to overlap: the pixel-split groups
-    // (below) have the lower latency (C4 1080p 5.6 vs 6.8 ms synchronised)
+    // (plan_groups) have the lower latency (C4 1080p 5.6 vs 6.8 ms synchronised)
     bool idle = !(c->batch_done && hipEventQuery(c->batch_done) != hipSuccess);
-    for (int q = 0; q < pipe_sets && idle; q++)
+    for (int q = 0; q < call.pipe_sets && idle; q++)
       if (c->set_free[q] && hipEventQuery(c->set_free[q]) != hipSuccess) idle = false;
     (void)hipGetLastError();  // (hipErrorNotReady is a status, not an error)
-    if (idle) pipe = false;
+    if (idle) call.pipe = false;
   }
-  if (!(fp->flags & RT_FLAG_MEGAKERNEL) && n_frames > 0) {
-    int rc = RT_ERR_NOMEM;
-    if (pipe && n_trace_pre >= c->n_groups) {  // a pipelined batch: the whole call in one set
-      rc = alloc_wavefront(c, (size_t)n_trace_pre * nv);
-      if (rc == RT_ERR_NOMEM) {  // not both sets: this size runs as frame groups from now on
-        c->pipe_nomem_slots = std::min(c->pipe_nomem_slots, (size_t)n_trace_pre * nv);
-        pipe = false;
-      } else if (rc) {
-        return rc;
-      }
+}
+
+// Path state for the call's batches (it only grows) and the frame groups' streams
+int reserve_path_state(rt_ctx* c, int n_frames, RenderCall& call) {
+  const int n = call.n_traced;
+  const size_t nv = std::max<size_t>(1, (size_t)c->n_valid);
+  int rc = RT_ERR_NOMEM;
+  if (call.pipe && n >= c->n_groups) {  // a pipelined batch: the whole call in one set
+    rc = alloc_wavefront(c, (size_t)n * nv);
+    if (rc == RT_ERR_NOMEM) {  // not both sets: this size runs as frame groups from now on
+      c->pipe_nomem_slots = std::min(c->pipe_nomem_slots, (size_t)n * nv);
+      call.pipe = false;
+    } else if (rc) {
+      return rc;
     }
-    while (rc == RT_ERR_NOMEM) {  // a budget larger than free HBM runs fewer frames at a time
-      const int per_group = (std::min(c->frames_cap, (int)n_frames) + c->n_groups - 1) / c->n_groups;
-      rc = alloc_wavefront(c, (size_t)per_group * nv);
-      if (rc != RT_ERR_NOMEM || per_group <= 1) break;
-      c->frames_cap = std::max(1, std::min(c->frames_cap, (int)n_frames) / 2);
-    }
-    if (rc) return rc;
-    for (int g = 1; g < c->n_groups; g++)
-      if (!c->aux[g]) HIPCHK(c, hipStreamCreateWithFlags(&c->aux[g], hipStreamNonBlocking));
   }
-  const int pset = pipe ? c->pipe_next : 0;
-  // the stream that runs this call: pipelined sets on aux[1], aux[2] (aux[1] is also the second
-  // frame group's stream: a pipelined call waits for unpipelined ones anyway, and a fourth stream
-  // measured as losing the overlap, GPU_MAX_HW_QUEUES being 4)
-  hipStream_t ps = pipe ? c->aux[1 + pset] : c->stream;
-  hipEvent_t e_entry = nullptr;  // pipelined: the caller's stream at entry (the blend waits for it)
-  if (pipe) {
-    c->pipe_next = (c->pipe_next + 1) % pipe_sets;
-    if (!ps) {
-      HIPCHK(c, hipStreamCreateWithFlags(&c->aux[1 + pset], hipStreamNonBlocking));
-      ps = c->aux[1 + pset];
-    }
-    if (c->cam_sets < pipe_sets) {  // one camera table per set (a call may move the camera)
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      dfree(c->d_cam);
-      HIPCHK(c, hipMalloc(&c->d_cam, 2 * (size_t)std::max(1, c->n_valid) * pipe_sets * sizeof(float4)));
-      c->cam_sets = pipe_sets;
-      c->wf.cam = c->d_cam;
-    }
-    e_entry = take_event(c);
-    if (!e_entry) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-    HIPCHK(c, hipEventRecord(e_entry, c->stream));
-    // the set's previous call and the last batched call have finished with its state
-    if (c->set_free[pset]) HIPCHK(c, hipStreamWaitEvent(ps, c->set_free[pset], 0));
-    if (c->batch_done) HIPCHK(c, hipStreamWaitEvent(ps, c->batch_done, 0));
+  while (rc == RT_ERR_NOMEM) {  // a budget larger than free HBM runs fewer frames at a time
+    const int per_group = (std::min(c->frames_cap, n_frames) + c->n_groups - 1) / c->n_groups;
+    rc = alloc_wavefront(c, (size_t)per_group * nv);
+    if (rc != RT_ERR_NOMEM || per_group <= 1) break;
+    c->frames_cap = std::max(1, std::min(c->frames_cap, n_frames) / 2);
   }
-  // The traced frames' (loopNum, randOrigin) go to a device table in one upload.
-  rt_ctx::FrameTable& T = c->ft[pipe ? 1 + pset : 0];
+  if (rc) return rc;
+  for (int g = 1; g < c->n_groups; g++)
+    if (!c->aux[g]) HIPCHK(c, hipStreamCreateWithFlags(&c->aux[g], hipStreamNonBlocking));
+  return RT_OK;
+}
+
+// The stream that runs this call: pipelined sets on aux[1], aux[2] (aux[1] is also the second
+// frame group's stream: a pipelined call waits for unpipelined ones anyway, and a fourth stream
+// measured as losing the overlap, GPU_MAX_HW_QUEUES being 4); every other call on the caller's
+int enter_pipelined_set(rt_ctx* c, RenderCall& call) {
+  call.pset = call.pipe ? c->pipe_next : 0;
+  call.ps = call.pipe ? c->aux[1 + call.pset] : c->stream;
+  if (!call.pipe) return RT_OK;
+  const int pset = call.pset, pipe_sets = call.pipe_sets;
+  c->pipe_next = (c->pipe_next + 1) % pipe_sets;
+  if (!call.ps) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->aux[1 + pset], hipStreamNonBlocking));
+    call.ps = c->aux[1 + pset];
+  }
+  if (c->cam_sets < pipe_sets) {  // one camera table per set (a call may move the camera)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_cam);
+    HIPCHK(c, hipMalloc(&c->d_cam, 2 * (size_t)std::max(1, c->n_valid) * pipe_sets * sizeof(float4)));
+    c->cam_sets = pipe_sets;
+    c->wf.cam = c->d_cam;
+  }
+  TAKE_EVENT(c, call.e_entry);
+  HIPCHK(c, hipEventRecord(call.e_entry, c->stream));
+  // the set's previous call and the last batched call have finished with its state
+  if (c->set_free[pset]) HIPCHK(c, hipStreamWaitEvent(call.ps, c->set_free[pset], 0));
+  if (c->batch_done) HIPCHK(c, hipStreamWaitEvent(call.ps, c->batch_done, 0));
+  return RT_OK;
+}
+
+// The traced frames' (loopNum, randOrigin) go to a device table in one upload; wf_sobol adds
+// their Sobol pairs and blend weights.  rt_ctx::loop_num moves here.
+int stage_frame_table(rt_ctx* c, const rt_frame_params* fp, int n_frames, RenderCall& call) {
+  const int n_traced = call.n_traced;
+  const bool wavefront = !(fp->flags & RT_FLAG_MEGAKERNEL);
+  rt_ctx::FrameTable& T = c->ft[call.pipe ? 1 + call.pset : 0];
   if (n_frames > 0 && (size_t)n_frames > T.cap) {
     if (T.ev) HIPCHK(c, hipEventSynchronize(T.ev));
     if (T.h) (void)hipHostFree(T.h);
     T.h = nullptr;
     if (T.d) HIPCHK(c, hipStreamSynchronize(c->stream));  // calls in flight read the old table
     dfree(T.d);
-    const size_t cap = std::max<size_t>(pipe ? 16 : 1024, (size_t)n_frames);
+    const size_t cap = std::max<size_t>(call.pipe ? 16 : 1024, (size_t)n_frames);
     HIPCHK(c, hipHostMalloc((void**)&T.h, 2 * cap * sizeof(int)));
     // device table: [cap] loop_num, [cap] rand_origin, then [cap][4] float2 Sobol pairs and [cap]
     // float2 blend weights (wf_sobol)
@@ -1446,465 +1530,414 @@ int rt_render_async(rt_ctx* c, const rt_frame_params* fp, const float* rand_orig
   }
   if (!T.ev) HIPCHK(c, hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
   HIPCHK(c, hipEventSynchronize(T.ev));  // the previous upload from this table has read T.h
-  int n_traced = 0;
-  for (int k = 0; k < n_frames; k++) {
-    if (fp->max_iterations == -1 || c->loop_num < fp->max_iterations) c->loop_num++;
-    if (!(fp->max_iterations == -1 || c->loop_num < fp->max_iterations)) continue;
-    T.h[n_traced] = c->loop_num;
-    memcpy(&T.h[T.cap + n_traced], &rand_origin[k], 4);
-    n_traced++;
+  c->loop_num = call.loop_end;
+  for (int k = 0; k < n_traced; k++) {
+    T.h[k] = call.frames[k].loop_num;
+    T.h[T.cap + k] = call.frames[k].ro_bits;
   }
   // small calls hand the pairs to wf_sobol as kernel arguments, which writes the table
   rtd::InlineFrames IF;
   memset(&IF, 0, sizeof(IF));
-  if (n_traced > 0 && n_traced <= RT_INLINE_FRAMES && !(fp->flags & RT_FLAG_MEGAKERNEL)) {
+  if (n_traced > 0 && n_traced <= RT_INLINE_FRAMES && wavefront) {
     IF.n_inline = n_traced;
     for (int k = 0; k < n_traced; k++) {
       IF.loop[k] = T.h[k];
       memcpy(&IF.ro[k], &T.h[T.cap + k], 4);
     }
   } else if (n_traced > 0) {
-    HIPCHK(c, hipMemcpyAsync(T.d, T.h, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, ps));
-    HIPCHK(c, hipMemcpyAsync(T.d + T.cap, T.h + T.cap, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, ps));
+    HIPCHK(c, hipMemcpyAsync(T.d, T.h, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, call.ps));
+    HIPCHK(c, hipMemcpyAsync(T.d + T.cap, T.h + T.cap, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, call.ps));
   }
-  HIPCHK(c, hipEventRecord(T.ev, ps));
-  const int* d_loop = T.d;
-  const float* d_ro = reinterpret_cast<const float*>(T.d + T.cap);
-  float2* d_sobol = reinterpret_cast<float2*>(T.d + 2 * T.cap);
-  float2* d_blendw = reinterpret_cast<float2*>(T.d + 10 * T.cap);
-  if (n_traced > 0 && !(fp->flags & RT_FLAG_MEGAKERNEL)) {
-    hipLaunchKernelGGL(rtd::wf_sobol, dim3((4 * n_traced + 255) / 256), dim3(256), 0, ps, T.d,
-                       reinterpret_cast<float*>(T.d + T.cap), d_sobol, d_blendw, n_traced, IF);
+  HIPCHK(c, hipEventRecord(T.ev, call.ps));
+  call.d_loop = T.d;
+  call.d_ro = reinterpret_cast<const float*>(T.d + T.cap);
+  call.d_sobol = reinterpret_cast<float2*>(T.d + 2 * T.cap);
+  call.d_blendw = reinterpret_cast<float2*>(T.d + 10 * T.cap);
+  if (n_traced > 0 && wavefront) {
+    hipLaunchKernelGGL(rtd::wf_sobol, dim3((4 * n_traced + 255) / 256), dim3(256), 0, call.ps, T.d,
+                       reinterpret_cast<float*>(T.d + T.cap), call.d_sobol, call.d_blendw, n_traced, IF);
     HIPCHK(c, hipGetLastError());
   }
-  // NEE light table for this call's envAngle (SampleHdrLight): the table built for this angle, or
-  // the other one rebuilt on this call's stream once the last call that read it has finished (a
-  // device-side wait: an interactive envAngle drag keeps its frames in flight)
-  rt_ctx::LightTable* LT = &c->light[c->light_cur];
-  if (n_traced > 0 && !(fp->flags & RT_FLAG_MEGAKERNEL)) {
-    auto same = [&](const rt_ctx::LightTable& t) {
-      return t.valid && __builtin_memcmp(&t.angle, &fp->env_angle, sizeof(float)) == 0;
-    };
+  return RT_OK;
+}
+
+// NEE light table for this call's envAngle (SampleHdrLight): the table built for this angle, or
+// the other one rebuilt on this call's stream once the last call that read it has finished (a
+// device-side wait: an interactive envAngle drag keeps its frames in flight)
+int bind_light_table(rt_ctx* c, const rt_frame_params* fp, RenderCall& call) {
+  rt_ctx::LightTable*& LT = call.LT;
+  LT = &c->light[c->light_cur];
+  if (call.n_traced <= 0 || (fp->flags & RT_FLAG_MEGAKERNEL)) return RT_OK;
+  auto same = [&](const rt_ctx::LightTable& t) {
+    return t.valid && __builtin_memcmp(&t.angle, &fp->env_angle, sizeof(float)) == 0;
+  };
+  if (!same(*LT)) {
+    const int other = c->light_cur ^ 1;
+    LT = &c->light[other];
+    c->light_cur = other;
     if (!same(*LT)) {
-      const int other = c->light_cur ^ 1;
-      LT = &c->light[other];
-      c->light_cur = other;
-      if (!same(*LT)) {
-        if (LT->last_use) HIPCHK(c, hipStreamWaitEvent(ps, LT->last_use, 0));
-        const rtd::Env E{c->d_hdr, c->d_cache, LT->d, c->hdr_w, c->hdr_h, c->hdr_res, fp->env_angle, fp->env_intensity};
-        const unsigned int n = (unsigned int)(c->hdr_w * c->hdr_h);
-        hipLaunchKernelGGL(rtd::rt_light_table_kernel, dim3(std::max(1u, std::min(4096u, (n + 255) / 256))), dim3(256),
-                           0, ps, E, LT->d);
-        HIPCHK(c, hipGetLastError());
-        if (!LT->built) HIPCHK(c, hipEventCreateWithFlags(&LT->built, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(LT->built, ps));
-        LT->angle = fp->env_angle;
-        LT->valid = true;
-      }
+      if (LT->last_use) HIPCHK(c, hipStreamWaitEvent(call.ps, LT->last_use, 0));
+      const rtd::Env E{c->d_hdr, c->d_cache, LT->d, c->hdr_w, c->hdr_h, c->hdr_res, fp->env_angle, fp->env_intensity};
+      const unsigned int n = (unsigned int)(c->hdr_w * c->hdr_h);
+      hipLaunchKernelGGL(rtd::rt_light_table_kernel, dim3(std::max(1u, std::min(4096u, (n + 255) / 256))), dim3(256),
+                         0, call.ps, E, LT->d);
+      HIPCHK(c, hipGetLastError());
+      if (!LT->built) HIPCHK(c, hipEventCreateWithFlags(&LT->built, hipEventDisableTiming));
+      HIPCHK(c, hipEventRecord(LT->built, call.ps));
+      LT->angle = fp->env_angle;
+      LT->valid = true;
     }
-    // every call that reads the table waits for its build, which may still run on another call's
-    // stream (a pipelined call on aux[1] rebuilt it; this one runs on aux[2] with the same angle)
-    if (LT->built) HIPCHK(c, hipStreamWaitEvent(ps, LT->built, 0));
   }
-  int done = 0;
-  while (done < n_traced) {
-    KParams P;
-    memset(&P, 0, sizeof(P));
+  // every call that reads the table waits for its build, which may still run on another call's
+  // stream (a pipelined call on aux[1] rebuilt it; this one runs on aux[2] with the same angle)
+  if (LT->built) HIPCHK(c, hipStreamWaitEvent(call.ps, LT->built, 0));
+  return RT_OK;
+}
+
+// The kernel parameters every batch of the call shares; the batch loop sets loop_num,
+// rand_origin, sobol, blend_w and n_frames
+void fill_kparams(const rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, KParams& P) {
+  memset(&P, 0, sizeof(P));
+  memcpy(P.pos, fp->position, 12); memcpy(P.lbc, fp->left_bottom_corner, 12);
+  memcpy(P.right, fp->right, 12); memcpy(P.up, fp->up, 12);
+  P.half_w = fp->half_w; P.half_h = fp->half_h;
+  P.enable_mis = fp->enable_mis; P.enable_env = fp->enable_env_map; P.enable_bsdf = fp->enable_bsdf;
+  P.env_intensity = fp->env_intensity; P.env_angle = fp->env_angle;
+  P.max_bounce = fp->max_bounce; P.flags = fp->flags;
+  P.W = c->W; P.H = c->H; P.tile_w = c->tile_w; P.tile_h = c->tile_h; P.tiles_x = c->tiles_x;
+  P.rank = c->rank; P.world = c->world; P.tile_ids = c->d_tile_ids;
+  P.tile_cost = c->tile_cost_on ? c->d_tile_cost : nullptr;
+  P.cost_blocks = c->cost_blocks ? 1 : 0;
+  P.n_work = (unsigned)c->local_tiles * (unsigned)(c->tile_w * c->tile_h);
+  P.nodes = c->d_nodes; P.root = c->root; P.has_scene = c->has_scene; P.stack_entries = c->stack_entries;
+  P.stack_cap = std::max(c->stack_entries, c->qstack_entries);
+  P.qnodes = c->d_qnodes; P.qroot = c->qroot; P.n_qnodes = c->n_qnodes; P.n_tri = c->n_tri;
+  {  // eps of the culling bound for this call's origins (camera position, scene points)
+    double R = c->cull_R;
+    for (int a = 0; a < 3; a++) R = std::max(R, std::fabs((double)fp->position[a]));
+    // x (1 + 2^-9): the fp32 rounding of eps * max|1/d| and of the sum in cull_limit
+    const double eps = 2.0 * (c->cull_K * 0x1p-24 * R * (1.0 + 0x1p-10) + c->cull_off) * (1.0 + 0x1p-9);
+    // RT_CULL_EPS_SCALE (tests only, read on every call): 0 restores the round-1 heuristic margin,
+    // whose hole tests/test_gpu_cull.py demonstrates
+    const char* es = knob("RT_CULL_EPS_SCALE");
+    const double sc = es ? atof(es) : 1.0;
+    P.cull_eps = (eps * sc < 1e30) ? (float)(eps * sc) : INFINITY;
+  }
+  P.tri = c->d_tri; P.trin = c->d_trin; P.hrec = c->d_hrec; P.mats = c->d_mats;
+  {  // edge-filter margin, rounded up (x (1 + 2^-20)); RT_TRI_MARGIN_SCALE (tests only, read on
+     // every call): 0 makes the filter decide every point, the negative control of
+     // tests/test_gpu_tri_filter.py
+    const char* ms = knob("RT_TRI_MARGIN_SCALE");
+    const double sc = ms ? atof(ms) : 1.0;
+    P.trx = c->d_trx;
+    P.tri_k1 = (float)(c->tri_k1 * sc * (1.0 + 0x1p-20));
+    P.tri_k0 = (float)(c->tri_k0 * sc * (1.0 + 0x1p-20));
+  }
+  P.hdr = c->d_hdr; P.cache = c->d_cache; P.light = call.LT->d;
+  P.hdr_w = c->hdr_w; P.hdr_h = c->hdr_h; P.hdr_res = c->hdr_res;
+  P.accum = c->d_accum; P.counter = c->d_counter; P.stats = c->d_stats;
+}
+
+// RT_FLAG_MEGAKERNEL: the batch in one persistent rt_path_kernel launch on the caller's stream
+int megakernel_batch(rt_ctx* c, const rt_frame_params* fp, const KParams& P) {
+  HIPCHK(c, hipMemsetAsync(c->d_counter, 0, 4, c->stream));
+  unsigned int max_blocks = (P.n_work + 255) / 256;
+  unsigned int grid = std::min<unsigned int>((unsigned)(c->n_cus * c->blocks_per_cu), max_blocks);
+  if (fp->flags & RT_FLAG_COUNT_VISITS)
+    hipLaunchKernelGGL(rtd::rt_path_kernel<true>, dim3(grid), dim3(256), c->block_lds, c->stream, P);
+  else
+    hipLaunchKernelGGL(rtd::rt_path_kernel<false>, dim3(grid), dim3(256), c->block_lds, c->stream, P);
+  HIPCHK(c, hipGetLastError());
+  c->trace_launches++;
+  return RT_OK;
+}
+
+// The groups of one wavefront batch (plan_groups), each with its own path state and stream
+struct GroupPlan {
+  int G = 1;
+  bool pix_split = false;
+  rtd::WFParams WG[rt_ctx::MAX_GROUPS];
+  hipStream_t sg[rt_ctx::MAX_GROUPS];
+  unsigned int slots_g[rt_ctx::MAX_GROUPS];
+  int split_g[rt_ctx::MAX_GROUPS] = {};
+  float4* cam = nullptr;           // this call's camera table (wf_camera writes it, every group reads it)
+  hipEvent_t prev_blend = nullptr; // after the previous frame group's blend (blend_and_join)
+};
+
+// Split the batch (P: P.n_frames frames) into frame groups (frames [f0, f1) each), one stream per
+// group; a batch of fewer frames than groups (one frame per call: the reference's own usage) is
+// split by pixels instead (work items [w0, w1) each, all frames), so the groups' latency-bound
+// late passes still overlap each other
+int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, const KParams& P, GroupPlan& plan) {
+  const bool pipe = call.pipe, count = (fp->flags & RT_FLAG_COUNT_VISITS) != 0;
+  const int nf = P.n_frames;
+  const bool pix_split = !pipe && !call.serial && pix_split_ok() && nf < c->n_groups && c->n_valid >= 64 * c->n_groups && !c->tile_cost_on;
+  const int G = (pipe || call.serial) ? 1 : pix_split ? c->n_groups : std::min(c->n_groups, nf);
+  plan.G = G;
+  plan.pix_split = pix_split;
+  const unsigned int trace_grid = (unsigned)(c->n_cus * std::max(c->trace_bpc, c->trace_bpc0));
+  unsigned long long* d_wave_log = nullptr;  // COUNT builds (RT_DEBUG_PASSES)
+#ifdef RT_DEV
+  if (int rc = dev_wave_log(c, d_wave_log)) return rc;
+#endif
+  const size_t ovf_group = c->stack_ovf_bytes / sizeof(int2) / (size_t)c->n_groups;
+  // pixel ranges of the groups: even, or after rt_order_work the costly head as group 0 and
+  // the rest split evenly (dev: RT_GROUP_SPLIT = group 0's share)
+  size_t b0 = std::min(c->order_head, (size_t)c->n_valid);
+#ifdef RT_DEV
+  if (const char* e = knob("RT_GROUP_SPLIT")) b0 = std::min((size_t)c->n_valid, ((size_t)((double)c->n_valid * atof(e)) + 63) / 64 * 64);
+#endif
+  auto wbound = [&](int g) -> unsigned int {
+    if (g <= 0) return 0u;
+    if (g >= G) return (unsigned)c->n_valid;
+    if (b0 > 0 && G > 1) return (unsigned)(b0 + ((size_t)c->n_valid - b0) * (g - 1) / (G - 1));
+    return (unsigned)((size_t)c->n_valid * g / G);
+  };
+  // the call's camera directions and camera hit points (WFState::org): one table of each per set
+  const size_t set_off = pipe ? (size_t)call.pset * (size_t)c->n_valid : 0;
+  plan.cam = c->wf.cam + set_off;
+  float4* const org = c->wf.cam + (size_t)c->cam_sets * (size_t)std::max(1, c->n_valid) + set_off;
+  for (int g = 0; g < G; g++) {
+    const int f0 = pix_split ? 0 : g * nf / G, f1 = pix_split ? nf : (g + 1) * nf / G;
+    const unsigned int w0 = pix_split ? wbound(g) : 0u;
+    const unsigned int w1 = pix_split ? wbound(g + 1) : (unsigned)c->n_valid;
+    rtd::WFParams& WP = plan.WG[g];
+    WP.K = P;
+    WP.K.loop_num = P.loop_num + f0;
+    WP.K.rand_origin = P.rand_origin + f0;
+    WP.K.sobol = P.sobol + 4 * f0;
+    WP.K.blend_w = P.blend_w + f0;
+    WP.K.n_frames = f1 - f0;
+    WP.K.n_work = w1 - w0;
+    WP.K.lds_entries = c->trace_lds_entries;
+    WP.K.pool_chunk = c->pool_chunk;
+    const int set = pipe ? call.pset : g;  // path-state set, overflow column, stream
+    WP.K.stack_ovf = c->d_stack_ovf ? c->d_stack_ovf + (size_t)set * ovf_group : nullptr;
+    WP.K.ovf_lanes = trace_grid * 256u;
+    {
+      const std::string e = ovf_layout_error(c, set, trace_grid);
+      if (!e.empty()) return fail(c, RT_ERR_STATE, e);
+    }
+    WP.K.wave_log = d_wave_log;
+#ifdef RT_DEV
+    // RT_DEBUG_WAVES_ONLY: the per-wave timeline without the per-ray step histogram (whose atomics
+    // on a few lines would set the pass times)
+    if (d_wave_log && knob("RT_DEBUG_WAVES_ONLY")) WP.K.flags |= rtd::kFlagNoRayHist;
+#endif
+    WP.S = c->wfg[set];
+    WP.S.pix_xy = c->wf.pix_xy + w0;
+    WP.S.pix_acc = c->wf.pix_acc + w0;
+    WP.S.cam = plan.cam + w0;
+    WP.S.org = org + w0;
+    WP.n_frames = f1 - f0;
+    WP.pass = 0;
+    WP.cam_n = 0u;
+    // (not for frame groups of one frame each: their blends must run in frame order)
+    WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
+    plan.slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
+    // bulk groups (the wf_shade<..., SH_SUB_BULK / CAM> launches) queue the two ray kinds apart
+    // (per pass in run_group_passes: passes 1 .. split_passes)
+    plan.split_g[g] = (c->split_kinds && c->wide && !count && !c->tile_cost_on && plan.slots_g[g] > c->finish_slots && !WP.fuse_blend) ? 1 : 0;
+    plan.sg[g] = pipe ? call.ps : g == 0 ? c->stream : c->aux[g];
+  }
+  return RT_OK;
+}
+
+// Camera directions of this call's pixels (every group reads them; wf_camera also zeroes the
+// groups' pass counters), then the aux streams start after everything already queued on the
+// caller's stream
+int launch_camera_and_fork(rt_ctx* c, const RenderCall& call, GroupPlan& plan) {
+  rtd::WFParams WC = plan.WG[0];
+  WC.K.n_work = (unsigned)c->n_valid;
+  WC.S.pix_xy = c->wf.pix_xy;
+  WC.S.pix_acc = c->wf.pix_acc;
+  WC.S.cam = plan.cam;
+  rtd::GroupCounters Z;
+  memset(&Z, 0, sizeof(Z));
+  Z.n = plan.G;
+  for (int g = 0; g < plan.G; g++) Z.cnt[g] = plan.WG[g].S.cnt;
+  hipLaunchKernelGGL(rtd::wf_camera, dim3(std::max(1u, std::min<unsigned int>(2048u, ((unsigned)c->n_valid + 255) / 256))),
+                     dim3(256), 0, call.ps, WC, Z);
+  HIPCHK(c, hipGetLastError());
+  if (plan.G > 1) {
+    hipEvent_t es;
+    TAKE_EVENT(c, es);
+    HIPCHK(c, hipEventRecord(es, c->stream));
+    for (int g = 1; g < plan.G; g++) HIPCHK(c, hipStreamWaitEvent(plan.sg[g], es, 0));
+    c->event_pool.push_back(es);  // reusable once the waits are enqueued
+  }
+  return RT_OK;
+}
+
+// Group g's wavefront passes on its stream: trace + shade per pass, or the finisher from fin_pass
+int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, GroupPlan& plan, int g) {
+  rtd::WFParams& WP = plan.WG[g];  // (its pass counters were zeroed by wf_camera)
+  const hipStream_t st = plan.sg[g];
+  const unsigned int slots = plan.slots_g[g];
+  const bool count = (fp->flags & RT_FLAG_COUNT_VISITS) != 0, bsdf = fp->enable_bsdf != 0;
+  const int last_pass = std::max(0, fp->max_bounce);
+  // small groups (one frame per call) end their paths in wf_finish after pass finish_pass-1
+  int fin_pass = (call.pipe && c->pipe_finish_pass >= 0) ? c->pipe_finish_pass : c->finish_pass;
+#ifdef RT_DEV
+  {
+    char kn[32];
+    snprintf(kn, sizeof(kn), "RT_FINISH_PASS_G%d", g);
+    if (const char* e = knob(kn)) fin_pass = std::max(0, atoi(e));
+  }
+#endif
+  const bool finish = !count && !c->tile_cost_on && !(fp->flags & RT_FLAG_NO_FINISH) &&
+                      fin_pass >= 1 && fin_pass <= last_pass &&
+                      ((fp->flags & RT_FLAG_FINISH) || slots <= c->finish_slots);
+  // pass 0 queues 16-B rays (WFState::org) unless the finisher takes them over at pass 1
+  WP.p1_compact = (finish && fin_pass <= 1) ? 0 : 1;
+  for (int pass = 0; pass <= last_pass; pass++) {
+    WP.pass = pass;
+    WP.split = (plan.split_g[g] && pass >= 1 && pass <= c->split_passes) ? 1 : 0;
+    WP.split_out = (plan.split_g[g] && pass + 1 <= c->split_passes) ? 1 : 0;
+    if (finish && pass == fin_pass) {
+      const dim3 fgrid((unsigned)(c->n_cus * (call.pipe ? c->pipe_finish_bpc : c->finish_bpc)));
+#ifdef RT_DEV
+      if (dev_passes()) return dev_finish_report(c, bsdf, fgrid, st, WP, g, pass);
+#endif
+      launch_finish(c, bsdf, fgrid, st, WP);
+      HIPCHK(c, hipGetLastError());
+      break;
+    }
+    // pass 0's camera paths are implicit (wf_trace / wf_shade generate them)
+    WP.cam_n = pass == 0 ? slots : 0u;
+    hipEvent_t t0, t1;
+    TAKE_EVENT(c, t0);
+    TAKE_EVENT(c, t1);
+    HIPCHK(c, hipEventRecord(t0, st));
+    launch_trace(c, count, dim3((unsigned)(c->n_cus * (pass == 0 ? c->trace_bpc0 : c->trace_bpc))), WP, st,
+                 slots <= c->finish_slots);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(t1, st));
+    c->trace_events.push_back({t0, t1, c->launches});
+    c->trace_launches++;
+#ifdef RT_DEV
+    if (dev_passes()) if (int rc = dev_pass_report(c, st, WP, g, pass, t0, t1)) return rc;
+#endif
+    const bool bulk = slots > c->finish_slots && !WP.fuse_blend;
+    const bool cam = RT_CAM_SHADE && bulk && WP.cam_n && WP.n_frames >= 64;
+    launch_shade(bsdf, WP.fuse_blend ? ShadeKind::fused : cam ? ShadeKind::cam : bulk ? ShadeKind::bulk : ShadeKind::plain,
+                 slots, st, WP);
+    HIPCHK(c, hipGetLastError());
+  }
+  return RT_OK;
+}
+
+// Group g's blend into the accumulation and, after the last group's, the caller's stream joins
+// the groups
+int blend_and_join(rt_ctx* c, RenderCall& call, GroupPlan& plan, int g) {
+  const hipStream_t st = plan.sg[g];
+  const int G = plan.G;
+  // progressive blend in frame order: group g after group g-1 (pixel groups blend
+  // disjoint pixels: no order between them)
+  if (plan.prev_blend) {
+    HIPCHK(c, hipStreamWaitEvent(st, plan.prev_blend, 0));
+    c->event_pool.push_back(plan.prev_blend);
+    plan.prev_blend = nullptr;
+  }
+  if (call.e_entry) {  // pipelined: after the caller's work on the accumulation and the previous call
+    HIPCHK(c, hipStreamWaitEvent(st, call.e_entry, 0));
+    c->event_pool.push_back(call.e_entry);  // reusable once the wait is enqueued
+    call.e_entry = nullptr;
+  }
+  if (!plan.WG[g].fuse_blend) {
+    hipLaunchKernelGGL(rtd::wf_blend, dim3(std::max(1u, std::min<unsigned int>(2048u, ((unsigned)c->n_valid + 255) / 256))),
+                       dim3(256), 0, st, plan.WG[g]);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (!plan.pix_split && g + 1 < G) {
+    TAKE_EVENT(c, plan.prev_blend);
+    HIPCHK(c, hipEventRecord(plan.prev_blend, st));
+  }
+  if (g + 1 < G) return RT_OK;
+  // the caller's stream joins the last group (frame groups finish in order through their
+  // blends) or every group (pixel groups)
+  for (int j = plan.pix_split ? 1 : G - 1; j < G && G > 1; j++) {
+    hipEvent_t ej;
+    TAKE_EVENT(c, ej);
+    HIPCHK(c, hipEventRecord(ej, plan.sg[j]));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, ej, 0));
+    c->event_pool.push_back(ej);
+  }
+  return RT_OK;
+}
+
+// The batch's end on the call's stream: its timing pair, what later calls wait for, and the
+// folds that bound the pending events
+int close_batch(rt_ctx* c, const RenderCall& call, hipEvent_t e0, hipEvent_t e1) {
+  const int pset = call.pset;
+  HIPCHK(c, hipEventRecord(e1, call.ps));
+  if (call.pipe) {  // the caller's stream joins the call; the set is free again after it
+    if (c->set_free[pset]) c->event_pool.push_back(c->set_free[pset]);
+    TAKE_EVENT(c, c->set_free[pset]);
+    HIPCHK(c, hipEventRecord(c->set_free[pset], call.ps));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->set_free[pset], 0));
+  } else if (call.pipe_sets >= 2) {  // pipelined calls that follow start after this batch
+    if (!c->batch_done) HIPCHK(c, hipEventCreateWithFlags(&c->batch_done, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->batch_done, c->stream));
+  }
+  if (!call.LT->last_use) HIPCHK(c, hipEventCreateWithFlags(&call.LT->last_use, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(call.LT->last_use, c->stream));
+  c->events.push_back({e0, e1});
+  c->launches++;
+  if (int rc = fold_trace_events(c, kMaxPendingEvents)) return rc;
+  return fold_events(c, c->events, c->kernel_ms, kMaxPendingEvents);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_async(rt_ctx* c, const rt_frame_params* fp, const float* rand_origin, int32_t n_frames) {
+  if (!c || !fp || n_frames < 0 || (n_frames && !rand_origin)) return RT_ERR_ARG;
+  if (!c->scene_set || !c->env_set || !c->frame_set) return fail(c, RT_ERR_STATE, "set_scene, set_env and resize first");
+  const bool mega = (fp->flags & RT_FLAG_MEGAKERNEL) != 0;
+  if (mega && !fp->enable_bsdf)
+    return fail(c, RT_ERR_ARG, "BRDF mode (enable_bsdf = 0) runs on the wavefront path only");
+  HIPCHK(c, hipSetDevice(c->device));
+  RenderCall call;
+  list_traced_frames(c, fp, rand_origin, n_frames, call);
+  admit_pipeline(c, fp, call);
+  if (!mega && n_frames > 0)
+    if (int rc = reserve_path_state(c, n_frames, call)) return rc;
+  if (int rc = enter_pipelined_set(c, call)) return rc;
+  if (int rc = stage_frame_table(c, fp, n_frames, call)) return rc;
+  if (int rc = bind_light_table(c, fp, call)) return rc;
+  KParams P;
+  fill_kparams(c, fp, call, P);
+  const size_t nv = std::max<size_t>(1, (size_t)c->n_valid);
+  for (int done = 0, nf = 0; done < call.n_traced; done += nf) {
     // RT_FLAG_SERIAL: one frame group per batch, as many frames as one group's path state holds
-    const int cap = (fp->flags & RT_FLAG_MEGAKERNEL) ? RT_MAX_FRAMES_PER_LAUNCH
-                    : serial ? (int)std::max<size_t>(1, std::min<size_t>((size_t)c->frames_cap, c->wf_paths / nv))
-                             : c->frames_cap;
-    const int nf = std::min(cap, n_traced - done);
-    P.loop_num = d_loop + done;
-    P.rand_origin = d_ro + done;
-    P.sobol = d_sobol + 4 * (size_t)done;
-    P.blend_w = d_blendw + done;
-    done += nf;
-    memcpy(P.pos, fp->position, 12); memcpy(P.lbc, fp->left_bottom_corner, 12);
-    memcpy(P.right, fp->right, 12); memcpy(P.up, fp->up, 12);
-    P.half_w = fp->half_w; P.half_h = fp->half_h;
-    P.enable_mis = fp->enable_mis; P.enable_env = fp->enable_env_map; P.enable_bsdf = fp->enable_bsdf;
-    P.env_intensity = fp->env_intensity; P.env_angle = fp->env_angle;
-    P.max_bounce = fp->max_bounce; P.flags = fp->flags; P.n_frames = nf;
-    P.W = c->W; P.H = c->H; P.tile_w = c->tile_w; P.tile_h = c->tile_h; P.tiles_x = c->tiles_x;
-    P.rank = c->rank; P.world = c->world; P.tile_ids = c->d_tile_ids;
-    P.tile_cost = c->tile_cost_on ? c->d_tile_cost : nullptr;
-    P.cost_blocks = c->cost_blocks ? 1 : 0;
-    P.n_work = (unsigned)c->local_tiles * (unsigned)(c->tile_w * c->tile_h);
-    P.nodes = c->d_nodes; P.root = c->root; P.has_scene = c->has_scene; P.stack_entries = c->stack_entries;
-    P.stack_cap = std::max(c->stack_entries, c->qstack_entries);
-    P.qnodes = c->d_qnodes; P.qroot = c->qroot; P.n_qnodes = c->n_qnodes; P.n_tri = c->n_tri;
-    {  // eps of the culling bound for this call's origins (camera position, scene points)
-      double R = c->cull_R;
-      for (int a = 0; a < 3; a++) R = std::max(R, std::fabs((double)fp->position[a]));
-      // x (1 + 2^-9): the fp32 rounding of eps * max|1/d| and of the sum in cull_limit
-      const double eps = 2.0 * (c->cull_K * 0x1p-24 * R * (1.0 + 0x1p-10) + c->cull_off) * (1.0 + 0x1p-9);
-      // RT_CULL_EPS_SCALE (tests only): 0 restores the round-1 heuristic margin, whose hole
-      // tests/test_gpu_cull.py demonstrates
-      const char* es = knob("RT_CULL_EPS_SCALE");
-      const double sc = es ? atof(es) : 1.0;
-      P.cull_eps = (eps * sc < 1e30) ? (float)(eps * sc) : INFINITY;
-    }
-    P.tri = c->d_tri; P.trin = c->d_trin; P.hrec = c->d_hrec; P.mats = c->d_mats;
-    {  // edge-filter margin, rounded up (x (1 + 2^-20)); RT_TRI_MARGIN_SCALE (tests only): 0 makes
-       // the filter decide every point, the negative control of tests/test_gpu_tri_filter.py
-      const char* ms = knob("RT_TRI_MARGIN_SCALE");
-      const double sc = ms ? atof(ms) : 1.0;
-      P.trx = c->d_trx;
-      P.tri_k1 = (float)(c->tri_k1 * sc * (1.0 + 0x1p-20));
-      P.tri_k0 = (float)(c->tri_k0 * sc * (1.0 + 0x1p-20));
-    }
-    P.hdr = c->d_hdr; P.cache = c->d_cache; P.light = LT->d;
-    P.hdr_w = c->hdr_w; P.hdr_h = c->hdr_h; P.hdr_res = c->hdr_res;
-    P.accum = c->d_accum; P.counter = c->d_counter; P.stats = c->d_stats;
-    if (P.n_work == 0) continue;
-    const bool count = (fp->flags & RT_FLAG_COUNT_VISITS) != 0;
-    hipEvent_t e0 = take_event(c), e1 = take_event(c);
-    if (!e0 || !e1) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-    HIPCHK(c, hipEventRecord(e0, ps));
-    if (fp->flags & RT_FLAG_MEGAKERNEL) {
-      HIPCHK(c, hipMemsetAsync(c->d_counter, 0, 4, c->stream));
-      unsigned int max_blocks = (P.n_work + 255) / 256;
-      unsigned int grid = std::min<unsigned int>((unsigned)(c->n_cus * c->blocks_per_cu), max_blocks);
-      if (count)
-        hipLaunchKernelGGL(rtd::rt_path_kernel<true>, dim3(grid), dim3(256), c->block_lds, c->stream, P);
-      else
-        hipLaunchKernelGGL(rtd::rt_path_kernel<false>, dim3(grid), dim3(256), c->block_lds, c->stream, P);
-      HIPCHK(c, hipGetLastError());
-      c->trace_launches++;
+    const int cap = mega ? RT_MAX_FRAMES_PER_LAUNCH
+                    : call.serial ? (int)std::max<size_t>(1, std::min<size_t>((size_t)c->frames_cap, c->wf_paths / nv))
+                                  : c->frames_cap;
+    nf = std::min(cap, call.n_traced - done);
+    P.loop_num = call.d_loop + done;
+    P.rand_origin = call.d_ro + done;
+    P.sobol = call.d_sobol + 4 * (size_t)done;
+    P.blend_w = call.d_blendw + done;
+    P.n_frames = nf;
+    if (P.n_work == 0) continue;  // an empty share: nothing to launch, nothing timed
+    hipEvent_t e0, e1;
+    TAKE_EVENT(c, e0);
+    TAKE_EVENT(c, e1);
+    HIPCHK(c, hipEventRecord(e0, call.ps));
+    if (mega) {
+      if (int rc = megakernel_batch(c, fp, P)) return rc;
     } else {
-      // split the batch into frame groups (frames [f0, f1) each), one stream per group; a batch
-      // of fewer frames than groups (one frame per call: the reference's own usage) is split by
-      // pixels instead (work items [w0, w1) each, all frames), so the groups' latency-bound late
-      // passes still overlap each other
-      const bool pix_split = !pipe && !serial && pix_ok && nf < c->n_groups && c->n_valid >= 64 * c->n_groups && !c->tile_cost_on;
-      const int G = (pipe || serial) ? 1 : pix_split ? c->n_groups : std::min(c->n_groups, nf);
-      const unsigned int trace_grid = (unsigned)(c->n_cus * std::max(c->trace_bpc, c->trace_bpc0));
-      const unsigned int trace_grid0 = (unsigned)(c->n_cus * c->trace_bpc0);
-      const unsigned int trace_grid1 = (unsigned)(c->n_cus * c->trace_bpc);
-#ifdef RT_DEV  // RT_DEBUG_PASSES: per-pass report of the COUNT build (syncs after every pass)
-      static const bool debug_passes = knob("RT_DEBUG_PASSES") != nullptr;
-      static unsigned long long* d_wave_log = nullptr;  // never freed
-      std::vector<unsigned long long> wave_log;
-      if (debug_passes) {
-        if (!d_wave_log) HIPCHK(c, hipMalloc(&d_wave_log, (size_t)trace_grid * 4 * 8 * sizeof(unsigned long long)));
-        wave_log.resize((size_t)trace_grid * 4 * 8);  // (the trace's records use the first half)
-      }
-#else
-      constexpr bool debug_passes = false;
-      unsigned long long* d_wave_log = nullptr;
-#endif
-      const size_t ovf_group = c->stack_ovf_bytes / sizeof(int2) / (size_t)c->n_groups;
-      rtd::WFParams WG[rt_ctx::MAX_GROUPS];
-      hipStream_t sg[rt_ctx::MAX_GROUPS];
-      unsigned int slots_g[rt_ctx::MAX_GROUPS];
-      int split_g[rt_ctx::MAX_GROUPS] = {};
-      // pixel ranges of the groups: even, or after rt_order_work the costly head as group 0 and
-      // the rest split evenly (dev: RT_GROUP_SPLIT = group 0's share)
-      size_t b0 = std::min(c->order_head, (size_t)c->n_valid);
-#ifdef RT_DEV
-      if (const char* e = knob("RT_GROUP_SPLIT")) b0 = std::min((size_t)c->n_valid, ((size_t)((double)c->n_valid * atof(e)) + 63) / 64 * 64);
-#endif
-      auto wbound = [&](int g) -> unsigned int {
-        if (g <= 0) return 0u;
-        if (g >= G) return (unsigned)c->n_valid;
-        if (b0 > 0 && G > 1) return (unsigned)(b0 + ((size_t)c->n_valid - b0) * (g - 1) / (G - 1));
-        return (unsigned)((size_t)c->n_valid * g / G);
-      };
-      for (int g = 0; g < G; g++) {
-        const int f0 = pix_split ? 0 : g * nf / G, f1 = pix_split ? nf : (g + 1) * nf / G;
-        const unsigned int w0 = pix_split ? wbound(g) : 0u;
-        const unsigned int w1 = pix_split ? wbound(g + 1) : (unsigned)c->n_valid;
-        rtd::WFParams& WP = WG[g];
-        WP.K = P;
-        WP.K.loop_num = P.loop_num + f0;
-        WP.K.rand_origin = P.rand_origin + f0;
-        WP.K.sobol = P.sobol + 4 * f0;
-        WP.K.blend_w = P.blend_w + f0;
-        WP.K.n_frames = f1 - f0;
-        WP.K.n_work = w1 - w0;
-        WP.K.lds_entries = c->trace_lds_entries;
-        WP.K.pool_chunk = c->pool_chunk;
-        const int set = pipe ? pset : g;  // path-state set, overflow column, stream
-        float4* cam = c->wf.cam + (pipe ? (size_t)pset * (size_t)c->n_valid : 0);
-        float4* org = c->wf.cam + (size_t)c->cam_sets * (size_t)std::max(1, c->n_valid) +
-                      (pipe ? (size_t)pset * (size_t)c->n_valid : 0);
-        WP.K.stack_ovf = c->d_stack_ovf ? c->d_stack_ovf + (size_t)set * ovf_group : nullptr;
-        WP.K.ovf_lanes = trace_grid * 256u;
-        {
-          const std::string e = ovf_layout_error(c, set, trace_grid);
-          if (!e.empty()) return fail(c, RT_ERR_STATE, e);
-        }
-        WP.K.wave_log = debug_passes ? d_wave_log : nullptr;  // COUNT builds (RT_DEBUG_PASSES)
-#ifdef RT_DEV
-        // RT_DEBUG_WAVES_ONLY: the per-wave timeline without the per-ray step histogram (whose atomics
-        // on a few lines would set the pass times)
-        if (debug_passes && knob("RT_DEBUG_WAVES_ONLY")) WP.K.flags |= rtd::kFlagNoRayHist;
-#endif
-        WP.S = c->wfg[set];
-        WP.S.pix_xy = c->wf.pix_xy + w0;
-        WP.S.pix_acc = c->wf.pix_acc + w0;
-        WP.S.cam = cam + w0;
-        WP.S.org = org + w0;
-        WP.n_frames = f1 - f0;
-        WP.pass = 0;
-        WP.cam_n = 0u;
-        // (not for frame groups of one frame each: their blends must run in frame order)
-        WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
-        slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
-        // bulk groups (the wf_shade<..., SH_SUB_BULK / CAM> launches) queue the two ray kinds apart
-        // (per pass below: passes 1 .. split_passes)
-        split_g[g] = (c->split_kinds && c->wide && !count && !c->tile_cost_on && slots_g[g] > c->finish_slots && !WP.fuse_blend) ? 1 : 0;
-        sg[g] = pipe ? ps : g == 0 ? c->stream : c->aux[g];
-      }
-      // camera directions of this call's pixels (every group reads them)
-      rtd::WFParams WC = WG[0];
-      WC.K.n_work = (unsigned)c->n_valid;
-      WC.S.pix_xy = c->wf.pix_xy;
-      WC.S.pix_acc = c->wf.pix_acc;
-      WC.S.cam = WG[0].S.cam;
-      rtd::GroupCounters Z;
-      memset(&Z, 0, sizeof(Z));
-      Z.n = G;
-      for (int g = 0; g < G; g++) Z.cnt[g] = WG[g].S.cnt;
-      hipLaunchKernelGGL(rtd::wf_camera, dim3(std::max(1u, std::min<unsigned int>(2048u, ((unsigned)c->n_valid + 255) / 256))),
-                         dim3(256), 0, ps, WC, Z);
-      HIPCHK(c, hipGetLastError());
-      // aux streams start after everything already queued on the caller's stream
-      if (G > 1) {
-        hipEvent_t es = take_event(c);
-        if (!es) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-        HIPCHK(c, hipEventRecord(es, c->stream));
-        for (int g = 1; g < G; g++) HIPCHK(c, hipStreamWaitEvent(sg[g], es, 0));
-        c->event_pool.push_back(es);  // reusable once the waits are enqueued
-      }
-      const int last_pass = std::max(0, fp->max_bounce);
-      const unsigned int blend_grid = std::max(1u, std::min<unsigned int>(2048u, ((unsigned)c->n_valid + 255) / 256));
-      hipEvent_t prev_blend = nullptr;
-      for (int g = 0; g < G; g++) {
-        rtd::WFParams& WP = WG[g];  // (its pass counters were zeroed by wf_camera)
-        // small groups (one frame per call) end their paths in wf_finish after pass finish_pass-1
-        int fin_pass = (pipe && c->pipe_finish_pass >= 0) ? c->pipe_finish_pass : c->finish_pass;
-#ifdef RT_DEV
-        {
-          char kn[32];
-          snprintf(kn, sizeof(kn), "RT_FINISH_PASS_G%d", g);
-          if (const char* e = knob(kn)) fin_pass = std::max(0, atoi(e));
-        }
-#endif
-        const bool finish = !count && !c->tile_cost_on && !(fp->flags & RT_FLAG_NO_FINISH) &&
-                            fin_pass >= 1 && fin_pass <= last_pass &&
-                            ((fp->flags & RT_FLAG_FINISH) || slots_g[g] <= c->finish_slots);
-        // pass 0 queues 16-B rays (WFState::org) unless the finisher takes them over at pass 1
-        WP.p1_compact = (finish && fin_pass <= 1) ? 0 : 1;
-        for (int pass = 0; pass <= last_pass; pass++) {
-          WP.pass = pass;
-          WP.split = (split_g[g] && pass >= 1 && pass <= c->split_passes) ? 1 : 0;
-          WP.split_out = (split_g[g] && pass + 1 <= c->split_passes) ? 1 : 0;
-          if (finish && pass == fin_pass) {
-            const dim3 fgrid((unsigned)(c->n_cus * (pipe ? c->pipe_finish_bpc : c->finish_bpc)));
-#ifdef RT_DEV
-            hipEvent_t ft0 = nullptr, ft1 = nullptr;
-            if (debug_passes) {
-              HIPCHK(c, hipMemsetAsync(d_wave_log, 0, wave_log.size() * 8, sg[g]));
-              ft0 = take_event(c); ft1 = take_event(c);
-              HIPCHK(c, hipEventRecord(ft0, sg[g]));
-            }
-#endif
-            if (fp->enable_bsdf) {
-              if (c->wide) hipLaunchKernelGGL((rtd::wf_finish<true, true>), fgrid, dim3(256), c->trace_lds, sg[g], WP);
-              else hipLaunchKernelGGL((rtd::wf_finish<true, false>), fgrid, dim3(256), c->trace_lds, sg[g], WP);
-            } else {
-              if (c->wide) hipLaunchKernelGGL((rtd::wf_finish<false, true>), fgrid, dim3(256), c->trace_lds, sg[g], WP);
-              else hipLaunchKernelGGL((rtd::wf_finish<false, false>), fgrid, dim3(256), c->trace_lds, sg[g], WP);
-            }
-            HIPCHK(c, hipGetLastError());
-#ifdef RT_DEV
-            if (debug_passes) {  // development aid: the finisher's waves (syncs!)
-              HIPCHK(c, hipEventRecord(ft1, sg[g]));
-              HIPCHK(c, hipStreamSynchronize(sg[g]));
-              float ms = 0.0f;
-              HIPCHK(c, hipEventElapsedTime(&ms, ft0, ft1));
-              c->event_pool.push_back(ft0);
-              c->event_pool.push_back(ft1);
-              HIPCHK(c, hipMemcpy(wave_log.data(), d_wave_log, wave_log.size() * 8, hipMemcpyDeviceToHost));
-              struct FW { double t0, t1, sh_us; unsigned long long it, sh, paths; double at[3]; unsigned long long it_at[3]; };
-              std::vector<FW> fw;
-              double tmin = 1e300;
-              for (size_t w = 0; w < wave_log.size() / 8; w++) {
-                const unsigned long long* e = &wave_log[8 * w];
-                if (!e[1]) continue;
-                FW f{e[0] / 100.0, e[1] / 100.0, e[3] / 100.0, e[2] & 0xfffffull, (e[2] >> 20) & 0xfffffull, e[2] >> 40, {}, {}};
-                for (int q = 0; q < 3; q++) {
-                  f.at[q] = e[4 + q] ? (double)(e[4 + q] & 0xffffffffull) / 100.0 : -1.0;
-                  f.it_at[q] = e[4 + q] >> 32;
-                }
-                fw.push_back(f);
-                tmin = std::min(tmin, e[0] / 100.0);
-              }
-              std::sort(fw.begin(), fw.end(), [](const FW& a, const FW& b) { return a.t1 > b.t1; });
-              unsigned long long paths = 0;
-              double life = 0.0, tail16 = 0.0, tail4 = 0.0;
-              for (const FW& f : fw) {
-                paths += f.paths;
-                life += f.t1 - f.t0;
-                if (f.at[0] >= 0) tail16 += f.t1 - f.t0 - f.at[0];
-                if (f.at[1] >= 0) tail4 += f.t1 - f.t0 - f.at[1];
-              }
-              fprintf(stderr, "[rt] finisher wave time with <= 16 / <= 4 lanes holding a path (list drained): %.3f / %.3f of %.0f "
-                      "wave-us\n", tail16 / std::max(1.0, life), tail4 / std::max(1.0, life), life);
-              fprintf(stderr, "[rt] group %d finisher from pass %d: %.3f ms, %zu waves, %llu paths; wave ends (us after the first "
-                      "start) 50%% %.1f 90%% %.1f 99%% %.1f 100%% %.1f\n", g, pass, ms, fw.size(), paths,
-                      fw.empty() ? 0.0 : fw[fw.size() / 2].t1 - tmin, fw.empty() ? 0.0 : fw[fw.size() / 10].t1 - tmin,
-                      fw.empty() ? 0.0 : fw[fw.size() / 100].t1 - tmin, fw.empty() ? 0.0 : fw[0].t1 - tmin);
-              for (size_t k = 0; k < std::min<size_t>(6, fw.size()); k++) {
-                const FW& f = fw[k];
-                fprintf(stderr, "[rt]   wave: start %.1f end %.1f us, %llu paths, %llu trace iterations (%.2f us each outside "
-                        "shade), %llu shade steps %.1f us (%.2f us each); <=16 / 4 / 1 busy lanes from %.0f / %.0f / %.0f us "
-                        "(iteration %llu / %llu / %llu)\n", f.t0 - tmin, f.t1 - tmin, f.paths, f.it,
-                        (f.t1 - f.t0 - f.sh_us) / (double)std::max(1ull, f.it), f.sh, f.sh_us, f.sh_us / (double)std::max(1ull, f.sh),
-                        f.at[0], f.at[1], f.at[2], f.it_at[0], f.it_at[1], f.it_at[2]);
-              }
-            }
-#endif
-            break;
-          }
-          // pass 0's camera paths are implicit (wf_trace / wf_shade generate them)
-          WP.cam_n = pass == 0 ? slots_g[g] : 0u;
-          hipEvent_t t0 = take_event(c), t1 = take_event(c);
-          if (!t0 || !t1) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-          HIPCHK(c, hipEventRecord(t0, sg[g]));
-          launch_trace(c, count, dim3(pass == 0 ? trace_grid0 : trace_grid1), WP, sg[g], slots_g[g] <= c->finish_slots);
-          HIPCHK(c, hipGetLastError());
-          HIPCHK(c, hipEventRecord(t1, sg[g]));
-          c->trace_events.push_back({t0, t1, c->launches});
-          c->trace_launches++;
-#ifdef RT_DEV
-          if (debug_passes) {  // development aid: per-pass rays / visits / duration (syncs!)
-            unsigned long long h[16];
-            unsigned int q[8];
-            HIPCHK(c, hipStreamSynchronize(sg[g]));
-            float ms = 0.0f;
-            HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
-            HIPCHK(c, hipMemcpy(h, c->d_stats, sizeof(h), hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(q, WP.S.cnt, sizeof(q), hipMemcpyDeviceToHost));
-            q[0] = q[rtd::cq(pass & 1)] + (WP.split ? q[rtd::cqs(pass & 1)] : 0u);  // (split queues: both kinds)
-            fprintf(stderr, "[rt] group %d pass %d: %u rays %.3f ms  cum internal %llu leaf %llu tri %llu iters %llu "
-                    "wave-iters max %llu ray-steps max %llu\n", g, pass, (WP.cam_n ? WP.cam_n : q[0]), ms, h[2], h[3], h[4], h[5], h[6], h[7]);
-            unsigned long long hq[6];
-            HIPCHK(c, hipMemcpy(hq, c->d_stats + 22, sizeof(hq), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[rt]   4-wide node visits with BFS index < 1 / 5 / 21 / 64 / 85 / 341: %llu %llu %llu %llu %llu %llu\n",
-                    hq[0], hq[1], hq[2], hq[3], hq[4], hq[5]);
-            HIPCHK(c, hipMemset(c->d_stats + 22, 0, sizeof(hq)));
-            fprintf(stderr, "[rt]   lane utilisation: node phase %.3f (%llu iters)  tri phase %.3f (%llu iters)  busy at "
-                    "refill %.3f (%llu outer)\n", h[9] / (64.0 * (double)(h[8] + !h[8])), h[8],
-                    h[11] / (64.0 * (double)(h[10] + !h[10])), h[10], h[13] / (64.0 * (double)(h[12] + !h[12])), h[12]);
-            fprintf(stderr, "[rt]   overflow-column pushes %llu (%.3f per ray)\n", h[14],
-                    (double)h[14] / (double)std::max(1u, WP.cam_n ? WP.cam_n : q[0]));
-            HIPCHK(c, hipMemset(c->d_stats + 6, 0, 10 * sizeof(unsigned long long)));
-            {  // steps-per-ray histogram (16-step buckets) by ray kind
-              unsigned long long hh[64];
-              HIPCHK(c, hipMemcpy(hh, c->d_stats + 32, sizeof(hh), hipMemcpyDeviceToHost));
-              static const char* kinds[4] = {"cont miss", "cont hit ", "shad miss", "shad hit "};
-              for (int kd = 0; kd < 4; kd++) {
-                fprintf(stderr, "[rt]   steps/ray %s:", kinds[kd]);
-                for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", hh[kd * 16 + b]);
-                fprintf(stderr, "\n");
-              }
-              HIPCHK(c, hipMemset(c->d_stats + 32, 0, sizeof(hh)));
-            }
-            if (WP.K.wave_log) {
-              HIPCHK(c, hipMemcpy(wave_log.data(), d_wave_log, wave_log.size() * 8, hipMemcpyDeviceToHost));
-              unsigned long long t0min = ~0ull, t1max = 0, t0max = 0, dmax = 0, itmax = 0, rmax = 0, cmax = 0;
-              std::vector<unsigned long long> ends;
-              double clk_sum = 0.0, wt_sum = 0.0;
-              for (size_t w = 0; w < wave_log.size() / 8; w++) {  // (trace_grid * 4 waves, 4 words each)
-                const unsigned long long* e = &wave_log[4 * w];
-                const unsigned long long its = e[2] & 0xfffffull, cyc = e[2] >> 20;
-                t0min = std::min(t0min, e[0]); t0max = std::max(t0max, e[0]); t1max = std::max(t1max, e[1]);
-                if (e[1] - e[0] > dmax) { dmax = e[1] - e[0]; itmax = its; rmax = e[3]; cmax = cyc; }
-                if (e[1] > e[0]) { clk_sum += (double)cyc; wt_sum += (double)(e[1] - e[0]); }
-                ends.push_back(e[1]);
-              }
-              fprintf(stderr, "[rt]   shader clock: mean over waves %.0f MHz, longest wave %.0f MHz\n",
-                      wt_sum > 0 ? 100.0 * clk_sum / wt_sum : 0.0, dmax ? 100.0 * (double)cmax / (double)dmax : 0.0);
-              std::sort(ends.begin(), ends.end());
-              auto us = [](unsigned long long t) { return t / 100.0; };  // wall_clock64 = 100 MHz
-              fprintf(stderr, "[rt]   waves: start spread %.1f us, span %.1f us; 50%% done at %.1f us, 90%% at %.1f, "
-                      "99%% at %.1f; longest wave %.1f us (%llu iters, %llu rays)\n", us(t0max - t0min),
-                      us(t1max - t0min), us(ends[ends.size() / 2] - t0min), us(ends[ends.size() * 9 / 10] - t0min),
-                      us(ends[ends.size() * 99 / 100] - t0min), us(dmax), itmax, rmax);
-            }
-          }
-#endif
-          // (bulk groups: RT_SH_SUB_BULK paths per thread and block-iteration)
-          const bool bulk_shade = slots_g[g] > c->finish_slots && !WP.fuse_blend;
-          // (the camera pass of a bulk group with >= 64 frames: camera-hit records, wf_shade<..., CAM>)
-          const bool cam_shade = RT_CAM_SHADE && bulk_shade && WP.cam_n && WP.n_frames >= 64;
-          const unsigned int sub = cam_shade ? (unsigned)rtd::SH_SUB_CAM : bulk_shade ? (unsigned)rtd::SH_SUB_BULK : (unsigned)rtd::SH_SUB;
-          const unsigned int shade_grid = std::max(1u, std::min<unsigned int>(4096u, (slots_g[g] + 256u * sub - 1) / (256u * sub)));
-          if (fp->enable_bsdf) {
-            if (WP.fuse_blend) hipLaunchKernelGGL((rtd::wf_shade<true, true>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-            else if (cam_shade) hipLaunchKernelGGL((rtd::wf_shade<true, false, rtd::SH_SUB_CAM, true>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-            else if (bulk_shade) hipLaunchKernelGGL((rtd::wf_shade<true, false, rtd::SH_SUB_BULK>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-            else hipLaunchKernelGGL((rtd::wf_shade<true, false>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-          } else {
-            if (WP.fuse_blend) hipLaunchKernelGGL((rtd::wf_shade<false, true>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-            else if (cam_shade) hipLaunchKernelGGL((rtd::wf_shade<false, false, rtd::SH_SUB_CAM, true>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-            else if (bulk_shade) hipLaunchKernelGGL((rtd::wf_shade<false, false, rtd::SH_SUB_BULK>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-            else hipLaunchKernelGGL((rtd::wf_shade<false, false>), dim3(shade_grid), dim3(256), 0, sg[g], WP);
-          }
-          HIPCHK(c, hipGetLastError());
-        }
-        // progressive blend in frame order: group g after group g-1 (pixel groups blend
-        // disjoint pixels: no order between them)
-        if (prev_blend) {
-          HIPCHK(c, hipStreamWaitEvent(sg[g], prev_blend, 0));
-          c->event_pool.push_back(prev_blend);
-        }
-        if (e_entry) {  // pipelined: after the caller's work on the accumulation and the previous call
-          HIPCHK(c, hipStreamWaitEvent(sg[g], e_entry, 0));
-          c->event_pool.push_back(e_entry);  // reusable once the wait is enqueued
-          e_entry = nullptr;
-        }
-        if (!WP.fuse_blend) {
-          hipLaunchKernelGGL(rtd::wf_blend, dim3(blend_grid), dim3(256), 0, sg[g], WP);
-          HIPCHK(c, hipGetLastError());
-        }
-        if (!pix_split && g + 1 < G) {
-          prev_blend = take_event(c);
-          if (!prev_blend) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-          HIPCHK(c, hipEventRecord(prev_blend, sg[g]));
-        }
-      }
-      // the caller's stream joins the last group (frame groups finish in order through their
-      // blends) or every group (pixel groups)
-      for (int g = pix_split ? 1 : G - 1; g < G && G > 1; g++) {
-        hipEvent_t ej = take_event(c);
-        if (!ej) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-        HIPCHK(c, hipEventRecord(ej, sg[g]));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, ej, 0));
-        c->event_pool.push_back(ej);
+      GroupPlan plan;
+      if (int rc = plan_groups(c, fp, call, P, plan)) return rc;
+      if (int rc = launch_camera_and_fork(c, call, plan)) return rc;
+      for (int g = 0; g < plan.G; g++) {
+        if (int rc = run_group_passes(c, fp, call, plan, g)) return rc;
+        if (int rc = blend_and_join(c, call, plan, g)) return rc;
       }
     }
-    HIPCHK(c, hipEventRecord(e1, ps));
-    if (pipe) {  // the caller's stream joins the call; the set is free again after it
-      if (c->set_free[pset]) c->event_pool.push_back(c->set_free[pset]);
-      c->set_free[pset] = take_event(c);
-      if (!c->set_free[pset]) return fail(c, RT_ERR_HIP, "hipEventCreate failed");
-      HIPCHK(c, hipEventRecord(c->set_free[pset], ps));
-      HIPCHK(c, hipStreamWaitEvent(c->stream, c->set_free[pset], 0));
-    } else if (pipe_sets >= 2) {  // pipelined calls that follow start after this batch
-      if (!c->batch_done) HIPCHK(c, hipEventCreateWithFlags(&c->batch_done, hipEventDisableTiming));
-      HIPCHK(c, hipEventRecord(c->batch_done, c->stream));
-    }
-    if (!LT->last_use) HIPCHK(c, hipEventCreateWithFlags(&LT->last_use, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(LT->last_use, c->stream));
-    c->events.push_back({e0, e1});
-    c->launches++;
-    int frc = fold_trace_events(c, kMaxPendingEvents);
-    if (!frc) frc = fold_events(c, c->events, c->kernel_ms, kMaxPendingEvents);
-    if (frc) return frc;
+    if (int rc = close_batch(c, call, e0, e1)) return rc;
   }
   return RT_OK;
 }

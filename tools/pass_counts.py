@@ -4,7 +4,7 @@
     RT_DEBUG_PASSES=1 RT_FINISH_PASS=99 python3 tools/pass_counts.py [--config C3] [--frames 1]
 
 Loads lib/librtamd_dev.so, renders warm-up frames, then one call of --frames frames with the
-per-pass report (stderr) of rt_render.hip's RT_DEBUG_PASSES."""
+per-pass report (stderr) of RT_DEBUG_PASSES (dev_pass_report, csrc/hip/rt_dev_report.h)."""
 import argparse
 import sys
 from pathlib import Path
