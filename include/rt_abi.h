@@ -24,6 +24,9 @@
  *   rt_read_accum            <- reading the accumulation texture (Utility.h:19-30 SaveFrame reads it
  *                               after tone mapping; here the raw fp32 history)
  *   rt_accum_device / rt_assemble_frame <- (new) device-side tile gather for RCCL
+ *   rt_trace_rays(_device)   <- hitBVH on caller rays (RT:338-392; any-hit: the isHit that RT:1389 consumes)
+ *   rt_camera_rays / rt_first_hit(_device) / rt_pick <- the camera ray (RT:1520-1527) and its hitBVH
+ *                               record (RT:1519), per pixel, without the bounce loop
  *
  * Conventions: every function returns RT_OK (0) or a negative rt_err_*; nothing aborts.
  * A context is bound to one HIP device and is not thread-safe (one host thread per ctx),
@@ -50,8 +53,11 @@
  *    switched off was removed).
  * 6: rt_gather moves the tiles with RCCL when the contexts sit on distinct devices;
  *    rt_gather_ex chooses the transport, rt_gather_last_transport reports it.  Nothing else changed.
+ * 7: ray queries: rt_ray, rt_hit, RT_HIT_INVALID, RT_QUERY_*, rt_trace_rays, rt_trace_rays_device,
+ *    rt_camera_rays, rt_first_hit, rt_first_hit_device, rt_pick, rt_get_triangle_material.  Additive:
+ *    every ABI-6 entry point and struct is unchanged, and rendering computes what it did.
  * A binding checks rt_abi_version() at load time. */
-#define RT_ABI_VERSION 6
+#define RT_ABI_VERSION 7
 
 #ifdef __cplusplus
 extern "C" {
@@ -278,6 +284,72 @@ int rt_tonemap(rt_ctx* ctx, const float* frame_device, int32_t flags, uint8_t* r
  * rt_display_fetch waits for that slot's image and copies it out (width*height*3 bytes). */
 int rt_tonemap_async(rt_ctx* ctx, const float* frame_device, int32_t flags, int32_t slot);
 int rt_display_fetch(rt_ctx* ctx, int32_t slot, uint8_t* rgb8_host);
+
+/* ---- Ray queries (ABI 7): the traversal of the render (hitBVH, RT:338-392) on rays of the caller's,
+ * and the camera pass's hit record (RT:1519-1527) per pixel.  A query is queued on the ctx stream
+ * after the render calls queued before it (pipelined ones included) and leaves LoopNum, the
+ * accumulation, the path state, rt_order_work's order and every rt_stats field as they were.  Its
+ * buffers are the context's own (allocated on first use, at most one chunk of 4 Mi rays, 432 MiB, freed by
+ * rt_destroy); larger queries run as consecutive chunks.
+ * Out of scope: a tmax for any-hit rays (the reference's shadow rays have none, RT:1389: use
+ * RT_QUERY_CLOSEST and compare t), barycentrics / texture coordinates in rt_hit, and gathering
+ * queries across ranks (each context answers for its own scene copy and its own pixels). */
+typedef struct rt_ray {
+  float origin[3];
+  float dir[3];             /* any finite non-zero length (t is in units of it, RT:265) */
+} rt_ray;                   /* 24 bytes */
+
+/* The reference's HitRecord (RT:241-299, RT:330) of the closest hit, bit for bit.  A miss has
+ * triangle = -1, t = -1.0f and every other byte 0; a ray that was not traced (below) has
+ * triangle = RT_HIT_INVALID, t = -1.0f and every other byte 0. */
+typedef struct rt_hit {
+  float t;                  /* HitRecord.distance = t - 0.00001 (RT:284) */
+  float point[3];           /* hitPoint = origin + dir * t (RT:270) */
+  float normal[3];          /* the interpolated normal, negated when inside (RT:256-259, RT:290-297) */
+  int32_t inside;           /* isInside: dot(N, dir) > 0 (RT:256) */
+  int32_t triangle;         /* post-BVH triangle index (rt_update_materials' `first`) */
+  int32_t material;         /* index into the context's material table (rt_get_triangle_material) */
+  int32_t pad_[2];          /* 0 */
+} rt_hit;                   /* 48 bytes */
+
+enum { RT_HIT_INVALID = -2 };
+enum { RT_QUERY_CLOSEST = 0, RT_QUERY_ANY = 1 };   /* kind */
+enum { RT_QUERY_NO_CULL = 1 };                     /* flags: the exhaustive order of RT_FLAG_NO_CULL */
+
+/* hitBVH (RT:338-392) for n rays in host memory; synchronous.  out: rt_hit[n] (RT_QUERY_CLOSEST) or
+ * int32_t[n] (RT_QUERY_ANY: 1 occluded, 0 not -- the isHit of the reference's shadow ray, RT:1389;
+ * which of several hits ends the ray is not defined, only that there is one).  A ray with a
+ * non-finite component or an all-zero direction is not traced: RT_HIT_INVALID (in `triangle`, or
+ * as the any-hit value); the call still returns RT_OK.  n == 0: RT_OK.  RT_ERR_STATE before
+ * rt_set_scene; RT_ERR_ARG for a bad kind, unknown flags or null pointers. */
+int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, int64_t n, int32_t kind, int32_t flags, void* out);
+/* The same (hitBVH, RT:338-392) on device pointers: enqueued on the ctx stream, results valid after rt_synchronize or in
+ * stream order.  origin_bound >= |every origin component| (finite, >= 0): the culling margin is derived
+ * for origins within it (rt_trace_rays scans for it), and a ray outside it is not traced
+ * (RT_HIT_INVALID).  rays_dev and out_dev need 4-byte alignment (out_dev 16 for rt_hit). */
+int rt_trace_rays_device(rt_ctx* ctx, const void* rays_dev, int64_t n, int32_t kind, int32_t flags,
+                         float origin_bound, void* out_dev);
+/* The camera rays of this rank's pixels (RT:1520-1527, TexCoords of vertex_shader.glsl) as the render
+ * computes them: origin = position, dir normalised.  Layouts as rt_read_accum (rt_ray instead of 3
+ * floats; FRAME writes only this rank's pixels).  Only the camera fields of params are read. */
+int rt_camera_rays(rt_ctx* ctx, const rt_frame_params* params, rt_ray* rays, int32_t layout);
+/* First-hit frame: hitBVH's record (RT:1519) of every camera ray of this rank -- per-pixel depth,
+ * normal, triangle and material for denoisers, outlines and debug views.  Same layouts; synchronous. */
+int rt_first_hit(rt_ctx* ctx, const rt_frame_params* params, rt_hit* hits, int32_t layout);
+/* The same (RT:1519) into device memory, RT_LAYOUT_LOCAL_TILES (rt_hit[local_tiles * tile_h * tile_w]; tile
+ * pixels outside the frame are not written), enqueued on the ctx stream: the form a display or
+ * denoise pass consumes. */
+int rt_first_hit_device(rt_ctx* ctx, const rt_frame_params* params, void* hits_dev);
+/* One pixel's camera ray (RT:1520-1527) and its hit: px, py in the accumulation's convention (row 0
+ * = bottom).  RT_ERR_ARG for a pixel outside the frame or not owned by this rank.  Synchronous. */
+int rt_pick(rt_ctx* ctx, const rt_frame_params* params, int32_t px, int32_t py, rt_hit* hit);
+/* The material of a (post-BVH) triangle from the host copies (no device call): the 24 floats as
+ * rt_set_scene / rt_update_materials received them (the device entry keeps them verbatim and adds
+ * the derived ax, ay, RT:205-207, and the integer medium type), and its material-table index.
+ * Triangles with equal materials share an index; rt_update_materials moves its range to the index
+ * of the new material (a new one unless the table already holds it), so what a pick returns can
+ * be edited and fed back to rt_update_materials(triangle, 1, ...).  Either output may be NULL. */
+int rt_get_triangle_material(rt_ctx* ctx, int32_t triangle, rt_material* out, int32_t* material_id);
 
 #ifdef __cplusplus
 }

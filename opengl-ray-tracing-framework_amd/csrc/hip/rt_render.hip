@@ -20,6 +20,7 @@
 #include "rt_abi.h"
 #include "rt_kernels.h"
 #include "rt_wavefront.h"
+#include "rt_query.h"
 
 #ifndef RT_SPLIT_KINDS  // bulk groups trace shadow rays and continuations in launches of their own (round 6)
 #define RT_SPLIT_KINDS 1
@@ -200,6 +201,19 @@ struct rt_ctx {
   int pipe_finish_pass = -1;  // -1: finish_pass
   hipEvent_t set_free[MAX_GROUPS] = {};
   hipEvent_t batch_done = nullptr;
+  // Ray queries (rt_trace_rays, rt_first_hit, rt_pick; rt_query.h): buffers of their own, apart from
+  // the render's path-state sets (a pipelined render call queued after a query starts its passes
+  // while the query still runs), allocated on first use for at most one chunk of rays
+  struct Query {
+    void* mem = nullptr;
+    size_t cap = 0;              // rays the buffers hold
+    rtd::WFState S{};            // ra / rb (sa / sb, cam alias them), queue[0], res, cnt
+    float* d_in = nullptr;       // staged caller rays of the host entry points (rt_ray)
+    float4* d_out = nullptr;     // staged results (rt_hit, or int32 any-hit answers)
+    float* d_zero = nullptr;     // one 0.0f: KParams::rand_origin of the camera trace (read, unused)
+    int2* d_ovf = nullptr;       // the traversal's overflow stack of the query launches
+    size_t ovf_bytes = 0;
+  } q;
 };
 
 namespace {
@@ -984,6 +998,8 @@ int rt_destroy(rt_ctx* c) {
   dfree(c->d_tile_cost);
   dfree(c->d_cam);
   dfree(c->d_stack_ovf);
+  if (c->q.mem) (void)hipFree(c->q.mem);
+  dfree(c->q.d_ovf);
   dfree(c->d_disp);
   dfree(c->d_gather);
   for (auto& m : c->rccl_comms) (void)ncclCommDestroy(m);
@@ -1594,27 +1610,15 @@ int bind_light_table(rt_ctx* c, const rt_frame_params* fp, RenderCall& call) {
   return RT_OK;
 }
 
-// The kernel parameters every batch of the call shares; the batch loop sets loop_num,
-// rand_origin, sobol, blend_w and n_frames
-void fill_kparams(const rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, KParams& P) {
-  memset(&P, 0, sizeof(P));
-  memcpy(P.pos, fp->position, 12); memcpy(P.lbc, fp->left_bottom_corner, 12);
-  memcpy(P.right, fp->right, 12); memcpy(P.up, fp->up, 12);
-  P.half_w = fp->half_w; P.half_h = fp->half_h;
-  P.enable_mis = fp->enable_mis; P.enable_env = fp->enable_env_map; P.enable_bsdf = fp->enable_bsdf;
-  P.env_intensity = fp->env_intensity; P.env_angle = fp->env_angle;
-  P.max_bounce = fp->max_bounce; P.flags = fp->flags;
-  P.W = c->W; P.H = c->H; P.tile_w = c->tile_w; P.tile_h = c->tile_h; P.tiles_x = c->tiles_x;
-  P.rank = c->rank; P.world = c->world; P.tile_ids = c->d_tile_ids;
-  P.tile_cost = c->tile_cost_on ? c->d_tile_cost : nullptr;
-  P.cost_blocks = c->cost_blocks ? 1 : 0;
-  P.n_work = (unsigned)c->local_tiles * (unsigned)(c->tile_w * c->tile_h);
+// The scene's part of the kernel parameters: traversal structure, triangles, materials and the
+// culling bound for ray origins within origin_R of the axes (render calls: the camera position;
+// queries: the caller's rays)
+void fill_scene_kparams(const rt_ctx* c, double origin_R, KParams& P) {
   P.nodes = c->d_nodes; P.root = c->root; P.has_scene = c->has_scene; P.stack_entries = c->stack_entries;
   P.stack_cap = std::max(c->stack_entries, c->qstack_entries);
   P.qnodes = c->d_qnodes; P.qroot = c->qroot; P.n_qnodes = c->n_qnodes; P.n_tri = c->n_tri;
-  {  // eps of the culling bound for this call's origins (camera position, scene points)
-    double R = c->cull_R;
-    for (int a = 0; a < 3; a++) R = std::max(R, std::fabs((double)fp->position[a]));
+  {  // eps of the culling bound for these origins and the scene's points
+    const double R = std::max(c->cull_R, origin_R);
     // x (1 + 2^-9): the fp32 rounding of eps * max|1/d| and of the sum in cull_limit
     const double eps = 2.0 * (c->cull_K * 0x1p-24 * R * (1.0 + 0x1p-10) + c->cull_off) * (1.0 + 0x1p-9);
     // RT_CULL_EPS_SCALE (tests only, read on every call): 0 restores the round-1 heuristic margin,
@@ -1633,6 +1637,26 @@ void fill_kparams(const rt_ctx* c, const rt_frame_params* fp, const RenderCall& 
     P.tri_k1 = (float)(c->tri_k1 * sc * (1.0 + 0x1p-20));
     P.tri_k0 = (float)(c->tri_k0 * sc * (1.0 + 0x1p-20));
   }
+}
+
+// The kernel parameters every batch of the call shares; the batch loop sets loop_num,
+// rand_origin, sobol, blend_w and n_frames
+void fill_kparams(const rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, KParams& P) {
+  memset(&P, 0, sizeof(P));
+  memcpy(P.pos, fp->position, 12); memcpy(P.lbc, fp->left_bottom_corner, 12);
+  memcpy(P.right, fp->right, 12); memcpy(P.up, fp->up, 12);
+  P.half_w = fp->half_w; P.half_h = fp->half_h;
+  P.enable_mis = fp->enable_mis; P.enable_env = fp->enable_env_map; P.enable_bsdf = fp->enable_bsdf;
+  P.env_intensity = fp->env_intensity; P.env_angle = fp->env_angle;
+  P.max_bounce = fp->max_bounce; P.flags = fp->flags;
+  P.W = c->W; P.H = c->H; P.tile_w = c->tile_w; P.tile_h = c->tile_h; P.tiles_x = c->tiles_x;
+  P.rank = c->rank; P.world = c->world; P.tile_ids = c->d_tile_ids;
+  P.tile_cost = c->tile_cost_on ? c->d_tile_cost : nullptr;
+  P.cost_blocks = c->cost_blocks ? 1 : 0;
+  P.n_work = (unsigned)c->local_tiles * (unsigned)(c->tile_w * c->tile_h);
+  double origin_R = 0.0;  // the call's ray origins: the camera position, scene points
+  for (int a = 0; a < 3; a++) origin_R = std::max(origin_R, std::fabs((double)fp->position[a]));
+  fill_scene_kparams(c, origin_R, P);
   P.hdr = c->d_hdr; P.cache = c->d_cache; P.light = call.LT->d;
   P.hdr_w = c->hdr_w; P.hdr_h = c->hdr_h; P.hdr_res = c->hdr_res;
   P.accum = c->d_accum; P.counter = c->d_counter; P.stats = c->d_stats;
@@ -2393,6 +2417,330 @@ int rt_gather_ex(rt_ctx* const* ctxs, int32_t n, float* full_rgb, int32_t transp
   }
   cleanup();
   return rc;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------- ray queries
+namespace {
+
+// Rays per chunk of a query: the buffers below take 108 B per ray (24 B ray records, 4 B queue
+// entry, 8 B result words, 24 + 48 B staging of the host entry points), 432 MiB at 4 Mi rays.  A
+// chunk is one wf_trace launch, whose end waits for its longest rays, so larger chunks trace
+// faster: 16 Mi secondary rays on C3 at 2 / 4 / 8 / 16 Mi per chunk: 3.66 / 4.88 / 5.42 / 5.66
+// Grays/s closest hit, 5.01 / 7.19 / 8.21 / 8.64 any hit (profiles/query_bench_C3.md); 4 Mi takes
+// most of that for under half a GB.  RT_QUERY_CHUNK (development build) sets it, so a test can
+// cross chunk boundaries with a few thousand rays.
+constexpr size_t kQueryChunk = size_t(4) << 20;
+size_t query_chunk() {
+  if (const char* e = knob("RT_QUERY_CHUNK")) return (size_t)std::max(64, atoi(e));
+  return kQueryChunk;
+}
+
+// The query buffers for `rays` rays at a time (they only grow, to at most one chunk) and the
+// overflow stack of the query's trace grid
+int reserve_query(rt_ctx* c, size_t rays) {
+  rt_ctx::Query& q = c->q;
+  if (rays > q.cap) {
+    if (q.mem) {  // earlier queries on the stream may still use the old buffers
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      (void)hipFree(q.mem);
+      q.mem = nullptr;
+      q.cap = 0;
+    }
+    const size_t n = std::max<size_t>(rays, 1024);
+    const size_t bytes = n * (16 + 8 + 4 + 8 + 24 + 48) + rtd::kCntWords * 4 + 8 * 256;  // + carve padding
+    const hipError_t me = hipMalloc(&q.mem, bytes);
+    if (me == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      q.mem = nullptr;
+      return fail(c, RT_ERR_NOMEM, "query buffers do not fit in device memory");
+    }
+    HIPCHK(c, me);
+    char* p = static_cast<char*>(q.mem);
+    auto carve = [&](size_t b) { char* r = p; p += (b + 255) & ~size_t(255); return r; };
+    rtd::WFState& S = q.S;
+    S = rtd::WFState{};
+    S.ra = S.sa = S.cam = (float4*)carve(n * 16);  // one kind of ray per chunk
+    S.rb = S.sb = (float2*)carve(n * 8);
+    S.queue[0] = S.queue_s[0] = (int*)carve(n * 4);
+    S.res = (int*)carve(n * 8);
+    q.d_in = (float*)carve(n * 24);
+    q.d_out = (float4*)carve(n * 48);
+    S.cnt = (unsigned int*)carve(rtd::kCntWords * 4);
+    q.d_zero = (float*)carve(4);
+    HIPCHK(c, hipMemsetAsync(q.d_zero, 0, 4, c->stream));
+    q.cap = n;
+  }
+  const size_t lanes = (size_t)c->n_cus * std::max(c->trace_bpc, c->trace_bpc0) * 256;
+  const size_t need = (size_t)std::max(0, std::max(c->stack_entries, c->qstack_entries) - c->trace_lds_entries) * lanes * sizeof(int2);
+  if (need > q.ovf_bytes) {
+    if (q.d_ovf) HIPCHK(c, hipStreamSynchronize(c->stream));
+    dfree(q.d_ovf);
+    q.ovf_bytes = 0;
+    HIPCHK(c, hipMalloc(&q.d_ovf, need));
+    q.ovf_bytes = need;
+  }
+  return RT_OK;
+}
+
+// Kernel parameters of a query's launches: the scene, the culling bound for origins within
+// origin_R, and the trace's launch geometry with the query's own overflow stack
+void fill_query_params(const rt_ctx* c, double origin_R, int32_t flags, rtd::WFParams& WP) {
+  memset(&WP, 0, sizeof(WP));
+  KParams& P = WP.K;
+  fill_scene_kparams(c, origin_R, P);
+  P.flags = (flags & RT_QUERY_NO_CULL) ? RT_FLAG_NO_CULL : 0;
+  P.n_frames = 1;
+  P.rand_origin = c->q.d_zero;
+  P.lds_entries = c->trace_lds_entries;
+  P.pool_chunk = c->pool_chunk;
+  P.stack_ovf = c->q.d_ovf;
+  P.ovf_lanes = (unsigned)(c->n_cus * std::max(c->trace_bpc, c->trace_bpc0)) * 256u;
+  WP.S = c->q.S;
+  WP.n_frames = 1;
+}
+
+dim3 query_grid(size_t n) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>(2048, (n + 255) / 256))); }
+
+// One chunk of caller rays (device pointers, n <= the reserved size) on the ctx stream: setup,
+// trace, resolve
+int query_chunk_launch(rt_ctx* c, const rtd::WFParams& WP, const float* rays_dev, size_t n, int32_t kind,
+                       float origin_bound, void* out_dev) {
+  const bool any = kind == RT_QUERY_ANY;
+  // the any-hit kernel of split queues exists for the 4-wide tree; the binary tree's kernel takes
+  // both kinds from one queue
+  const bool any_kernel = any && c->wide;
+  HIPCHK(c, hipMemsetAsync(WP.S.cnt, 0, rtd::kCntWords * 4, c->stream));
+  const dim3 setup_grid((unsigned)std::min<size_t>(2048, (n + 4 * rtd::kSetupSpan - 1) / (4 * rtd::kSetupSpan)));
+  hipLaunchKernelGGL(rtd::wf_query_setup, setup_grid, dim3(256), 0, c->stream, WP.S, rays_dev, (unsigned)n,
+                     origin_bound, any ? 1 : 0, any_kernel ? rtd::cqs(0) : rtd::cq(0));
+  HIPCHK(c, hipGetLastError());
+  const dim3 grid((unsigned)(c->n_cus * c->trace_bpc));
+  if (any_kernel) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 2>), grid, dim3(256), c->trace_lds, c->stream, WP);
+  else if (c->wide) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 1>), grid, dim3(256), c->trace_lds, c->stream, WP);
+  else hipLaunchKernelGGL((rtd::wf_trace<false, false, false>), grid, dim3(256), c->trace_lds, c->stream, WP);
+  HIPCHK(c, hipGetLastError());
+  if (any) hipLaunchKernelGGL(rtd::wf_query_resolve_any, query_grid(n), dim3(256), 0, c->stream, WP.S, (unsigned)n, (int*)out_dev);
+  else hipLaunchKernelGGL(rtd::wf_query_resolve<false>, query_grid(n), dim3(256), 0, c->stream, WP, (unsigned)n, (float4*)out_dev);
+  HIPCHK(c, hipGetLastError());
+  return RT_OK;
+}
+
+int query_args(rt_ctx* c, const void* rays, int64_t n, int32_t kind, int32_t flags, const void* out) {
+  if (!c) return RT_ERR_ARG;
+  if (n < 0 || (kind != RT_QUERY_CLOSEST && kind != RT_QUERY_ANY) || (flags & ~RT_QUERY_NO_CULL))
+    return fail(c, RT_ERR_ARG, "bad ray count, kind or flags");
+  if (n > 0 && (!rays || !out)) return fail(c, RT_ERR_ARG, "null rays or output");
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "rt_set_scene first");
+  return RT_OK;
+}
+
+// The camera of a first-hit / camera-ray / pick call: finite fields, a sized frame
+int camera_args(rt_ctx* c, const rt_frame_params* fp, bool need_scene) {
+  if (!c || !fp) return RT_ERR_ARG;
+  if (!c->frame_set || (need_scene && !c->scene_set)) return fail(c, RT_ERR_STATE, need_scene ? "rt_set_scene and rt_resize first" : "rt_resize first");
+  bool ok = std::isfinite(fp->half_w) && std::isfinite(fp->half_h);
+  for (int a = 0; a < 3; a++)
+    ok = ok && std::isfinite(fp->position[a]) && std::isfinite(fp->left_bottom_corner[a]) && std::isfinite(fp->right[a]) &&
+         std::isfinite(fp->up[a]);
+  return ok ? RT_OK : fail(c, RT_ERR_ARG, "non-finite camera");
+}
+
+void fill_camera(const rt_ctx* c, const rt_frame_params* fp, KParams& P) {
+  memcpy(P.pos, fp->position, 12); memcpy(P.lbc, fp->left_bottom_corner, 12);
+  memcpy(P.right, fp->right, 12); memcpy(P.up, fp->up, 12);
+  P.half_w = fp->half_w; P.half_h = fp->half_h;
+  P.W = c->W; P.H = c->H;
+}
+
+double camera_R(const rt_frame_params* fp) {
+  double r = 0.0;
+  for (int a = 0; a < 3; a++) r = std::max(r, std::fabs((double)fp->position[a]));
+  return r;
+}
+
+// Records of `bytes` bytes each in local-tile order on the device -> the host buffer in `layout`
+// (rt_read_accum's layouts; FRAME writes only this rank's pixels)
+int tiles_to_host(rt_ctx* c, const void* tiles_dev, size_t bytes, void* host, int32_t layout) {
+  const size_t tpx = (size_t)c->tile_w * c->tile_h, n = (size_t)c->local_tiles * tpx;
+  if (layout == RT_LAYOUT_LOCAL_TILES) {
+    if (n) HIPCHK(c, hipMemcpyAsync(host, tiles_dev, n * bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+  }
+  std::vector<char> buf(std::max<size_t>(1, n * bytes));
+  if (n) HIPCHK(c, hipMemcpyAsync(buf.data(), tiles_dev, n * bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int lt = 0; lt < c->local_tiles; lt++) {
+    const int gt = c->my_tiles[lt], tx = gt % c->tiles_x, ty = gt / c->tiles_x;
+    for (int ly = 0; ly < c->tile_h; ly++) {
+      const int py = ty * c->tile_h + ly, px0 = tx * c->tile_w;
+      if (py >= c->H || px0 >= c->W) continue;
+      const size_t run = (size_t)std::min(c->tile_w, c->W - px0);
+      memcpy(static_cast<char*>(host) + ((size_t)py * c->W + px0) * bytes,
+             buf.data() + ((size_t)lt * tpx + (size_t)ly * c->tile_w) * bytes, run * bytes);
+    }
+  }
+  return RT_OK;
+}
+
+// The first-hit frame of this rank into hits_dev (local-tile order), on the ctx stream: the
+// implicit camera queue over wf_camera's table, a chunk of work items at a time
+int first_hit_launch(rt_ctx* c, const rt_frame_params* fp, float4* hits_dev) {
+  const size_t nv = (size_t)c->n_valid, chunk = query_chunk();
+  if (int rc = reserve_query(c, std::min(nv, chunk))) return rc;
+  rtd::WFParams WP;
+  fill_query_params(c, camera_R(fp), (fp->flags & RT_FLAG_NO_CULL) ? RT_QUERY_NO_CULL : 0, WP);
+  fill_camera(c, fp, WP.K);
+  for (size_t w0 = 0; w0 < nv; w0 += chunk) {
+    const unsigned int n = (unsigned)std::min(chunk, nv - w0);
+    WP.K.n_work = n;
+    WP.cam_n = n;
+    WP.S.pix_xy = c->wf.pix_xy + w0;
+    WP.S.pix_acc = c->wf.pix_acc + w0;
+    rtd::GroupCounters Z;
+    memset(&Z, 0, sizeof(Z));
+    Z.n = 1;
+    Z.cnt[0] = WP.S.cnt;
+    hipLaunchKernelGGL(rtd::wf_camera, query_grid(n), dim3(256), 0, c->stream, WP, Z);
+    HIPCHK(c, hipGetLastError());
+    const dim3 grid((unsigned)(c->n_cus * c->trace_bpc0));
+    if (c->wide) hipLaunchKernelGGL((rtd::wf_trace<false, true, true>), grid, dim3(256), c->trace_lds, c->stream, WP);
+    else hipLaunchKernelGGL((rtd::wf_trace<false, false, true>), grid, dim3(256), c->trace_lds, c->stream, WP);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(rtd::wf_query_resolve<true>, query_grid(n), dim3(256), 0, c->stream, WP, n, hits_dev);
+    HIPCHK(c, hipGetLastError());
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_trace_rays_device(rt_ctx* c, const void* rays_dev, int64_t n, int32_t kind, int32_t flags, float origin_bound,
+                         void* out_dev) {
+  if (int rc = query_args(c, rays_dev, n, kind, flags, out_dev)) return rc;
+  if (!(origin_bound >= 0.0f)) return fail(c, RT_ERR_ARG, "origin_bound must be >= 0");
+  if (n == 0) return RT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t chunk = query_chunk();
+  if (int rc = reserve_query(c, std::min((size_t)n, chunk))) return rc;
+  rtd::WFParams WP;
+  fill_query_params(c, (double)origin_bound, flags, WP);
+  const size_t out_bytes = kind == RT_QUERY_ANY ? sizeof(int32_t) : sizeof(rt_hit);
+  for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+    const size_t m = std::min(chunk, (size_t)n - i0);
+    if (int rc = query_chunk_launch(c, WP, static_cast<const float*>(rays_dev) + 6 * i0, m, kind, origin_bound,
+                                    static_cast<char*>(out_dev) + i0 * out_bytes))
+      return rc;
+  }
+  return RT_OK;
+}
+
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int64_t n, int32_t kind, int32_t flags, void* out) {
+  if (int rc = query_args(c, rays, n, kind, flags, out)) return rc;
+  if (n == 0) return RT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // the culling bound must cover the origins that are traced (a non-finite one never is)
+  float bound = 0.0f;
+  for (int64_t i = 0; i < n; i++)
+    for (int a = 0; a < 3; a++) {
+      const float o = std::fabs(rays[i].origin[a]);
+      if (std::isfinite(o)) bound = std::max(bound, o);
+    }
+  const size_t chunk = query_chunk();
+  if (int rc = reserve_query(c, std::min((size_t)n, chunk))) return rc;
+  rtd::WFParams WP;
+  fill_query_params(c, (double)bound, flags, WP);
+  const size_t out_bytes = kind == RT_QUERY_ANY ? sizeof(int32_t) : sizeof(rt_hit);
+  for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+    const size_t m = std::min(chunk, (size_t)n - i0);
+    HIPCHK(c, hipMemcpyAsync(c->q.d_in, rays + i0, m * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+    if (int rc = query_chunk_launch(c, WP, c->q.d_in, m, kind, bound, c->q.d_out)) return rc;
+    HIPCHK(c, hipMemcpyAsync(static_cast<char*>(out) + i0 * out_bytes, c->q.d_out, m * out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffers are reused by the next chunk
+  }
+  return RT_OK;
+}
+
+int rt_camera_rays(rt_ctx* c, const rt_frame_params* fp, rt_ray* rays, int32_t layout) {
+  if (int rc = camera_args(c, fp, false)) return rc;
+  if (!rays || (layout != RT_LAYOUT_FRAME && layout != RT_LAYOUT_LOCAL_TILES)) return fail(c, RT_ERR_ARG, "null rays or bad layout");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->local_tiles * c->tile_w * c->tile_h;
+  float* d = nullptr;  // (a one-off table of the whole frame: not the chunked query buffers)
+  HIPCHK(c, hipMalloc(&d, std::max<size_t>(1, n) * sizeof(rt_ray)));
+  KParams P;
+  memset(&P, 0, sizeof(P));
+  fill_camera(c, fp, P);
+  int rc = RT_OK;
+  if (c->n_valid > 0) {
+    hipLaunchKernelGGL(rtd::wf_query_camera, query_grid((size_t)c->n_valid), dim3(256), 0, c->stream, P, c->wf.pix_xy,
+                       c->wf.pix_acc, (unsigned)c->n_valid, 0u, d);
+    if (hipGetLastError() != hipSuccess) rc = fail(c, RT_ERR_HIP, "wf_query_camera launch failed");
+  }
+  if (!rc) rc = tiles_to_host(c, d, sizeof(rt_ray), rays, layout);
+  (void)hipFree(d);
+  return rc;
+}
+
+int rt_first_hit_device(rt_ctx* c, const rt_frame_params* fp, void* hits_dev) {
+  if (int rc = camera_args(c, fp, true)) return rc;
+  if (!hits_dev) return fail(c, RT_ERR_ARG, "null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  return first_hit_launch(c, fp, static_cast<float4*>(hits_dev));
+}
+
+int rt_first_hit(rt_ctx* c, const rt_frame_params* fp, rt_hit* hits, int32_t layout) {
+  if (int rc = camera_args(c, fp, true)) return rc;
+  if (!hits || (layout != RT_LAYOUT_FRAME && layout != RT_LAYOUT_LOCAL_TILES)) return fail(c, RT_ERR_ARG, "null hits or bad layout");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->local_tiles * c->tile_w * c->tile_h;
+  float4* d = nullptr;  // (the whole frame's records, tile pixels outside the frame zeroed)
+  HIPCHK(c, hipMalloc(&d, std::max<size_t>(1, n) * sizeof(rt_hit)));
+  int rc = RT_OK;
+  if (hipMemsetAsync(d, 0, std::max<size_t>(1, n) * sizeof(rt_hit), c->stream) != hipSuccess) rc = fail(c, RT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = first_hit_launch(c, fp, d);
+  if (!rc) rc = tiles_to_host(c, d, sizeof(rt_hit), hits, layout);
+  else (void)hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  return rc;
+}
+
+int rt_pick(rt_ctx* c, const rt_frame_params* fp, int32_t px, int32_t py, rt_hit* hit) {
+  if (int rc = camera_args(c, fp, true)) return rc;
+  if (!hit) return fail(c, RT_ERR_ARG, "null hit");
+  if (px < 0 || py < 0 || px >= c->W || py >= c->H) return fail(c, RT_ERR_ARG, "pixel outside the frame");
+  if (c->owner[(size_t)(py / c->tile_h) * c->tiles_x + px / c->tile_w] != c->rank)
+    return fail(c, RT_ERR_ARG, "pixel not owned by this rank");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = reserve_query(c, 1)) return rc;
+  // the pixel's camera ray as wf_camera computes it, then a closest-hit query of one ray
+  const float bound = (float)camera_R(fp);  // (exact: a float's magnitude)
+  rtd::WFParams WP;
+  fill_query_params(c, (double)bound, (fp->flags & RT_FLAG_NO_CULL) ? RT_QUERY_NO_CULL : 0, WP);
+  KParams PC;
+  memset(&PC, 0, sizeof(PC));
+  fill_camera(c, fp, PC);
+  hipLaunchKernelGGL(rtd::wf_query_camera, dim3(1), dim3(256), 0, c->stream, PC, (const unsigned int*)nullptr,
+                     (const unsigned int*)nullptr, 1u, (unsigned)px | ((unsigned)py << 16), c->q.d_in);
+  HIPCHK(c, hipGetLastError());
+  if (int rc = query_chunk_launch(c, WP, c->q.d_in, 1, RT_QUERY_CLOSEST, bound, c->q.d_out)) return rc;
+  HIPCHK(c, hipMemcpyAsync(hit, c->q.d_out, sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_get_triangle_material(rt_ctx* c, int32_t triangle, rt_material* out, int32_t* material_id) {
+  if (!c) return RT_ERR_ARG;
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "rt_set_scene first");
+  if (triangle < 0 || triangle >= c->n_tri) return fail(c, RT_ERR_ARG, "triangle outside the triangle list");
+  const int id = c->tri_mat[(size_t)triangle];
+  if (out) memcpy(out, &c->mat_table[32 * (size_t)id], sizeof(rt_material));  // pack_material keeps the 24 floats verbatim
+  if (material_id) *material_id = id;
+  return RT_OK;
 }
 
 }  // extern "C"

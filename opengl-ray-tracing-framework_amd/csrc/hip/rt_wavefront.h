@@ -205,6 +205,14 @@ struct GroupCounters {
   unsigned int* cnt[4];
   int n;
 };
+// the camera ray direction of pixel xy = px | py << 16 and its u * v (wf_camera, wf_query_camera)
+RTD float4 camera_dir(const KParams& P, f3 lbc, f3 right, f3 up, unsigned int xy) {
+  const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
+  const float u = ((float)px + 0.5f) / (float)P.W;  // TexCoords (vertex_shader.glsl)
+  const float v = ((float)py + 0.5f) / (float)P.H;
+  const f3 d = normalize(lbc + (u * 2.0f * P.half_w) * right + (v * 2.0f * P.half_h) * up);  // R6
+  return make_float4(d.x, d.y, d.z, u * v);
+}
 __global__ __launch_bounds__(256) void wf_camera(const WFParams W, const GroupCounters Z) {
   const KParams& P = W.K;
   const WFState& S = W.S;
@@ -213,14 +221,8 @@ __global__ __launch_bounds__(256) void wf_camera(const WFParams W, const GroupCo
   const f3 lbc = mk3(P.lbc[0], P.lbc[1], P.lbc[2]);
   const f3 right = mk3(P.right[0], P.right[1], P.right[2]);
   const f3 up = mk3(P.up[0], P.up[1], P.up[2]);
-  for (unsigned int w = blockIdx.x * blockDim.x + threadIdx.x; w < P.n_work; w += gridDim.x * blockDim.x) {
-    const unsigned int xy = S.pix_xy[w];
-    const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
-    const float u = ((float)px + 0.5f) / (float)P.W;  // TexCoords (vertex_shader.glsl)
-    const float v = ((float)py + 0.5f) / (float)P.H;
-    const f3 d = normalize(lbc + (u * 2.0f * P.half_w) * right + (v * 2.0f * P.half_h) * up);  // R6
-    S.cam[w] = make_float4(d.x, d.y, d.z, u * v);
-  }
+  for (unsigned int w = blockIdx.x * blockDim.x + threadIdx.x; w < P.n_work; w += gridDim.x * blockDim.x)
+    S.cam[w] = camera_dir(P, lbc, right, up, S.pix_xy[w]);
 }
 
 // Per frame of a render call: sobolVec2(loopNum + 1, bounce) of RT:616-620 for bounces 0..3

@@ -135,6 +135,7 @@ class Input:
     camera_zoom: Optional[float] = None                 # SliderFloat "Camera Zoom"
     materials: Sequence[tuple] = ()             # (first_triangle, count, sl.Material): setDirty()
     resize: Optional[tuple] = None              # (width, height)
+    pick: Optional[tuple] = None                # cursor (xpos, ypos), window coordinates like `mouse`
 
 
 class Session:
@@ -226,6 +227,7 @@ class Session:
         if self.camera.take_reset() or reset:
             self.r.reset()
         fp = self.frame_params()
+        picked = self._pick(fp, *inp.pick) if inp.pick is not None else None
         ro = self._rand[self.frame:self.frame + 1]
         self.frame += 1
         # LoopIncrease under maxIterations happens inside (main.cpp:175)
@@ -234,6 +236,8 @@ class Session:
         else:
             self.r.render(fp, ro)
         out = {"params": fp, "loop_num": self.r.loop_num, "rand_origin": float(ro[0]), "delta_time": delta_time}
+        if picked is not None:
+            out["pick"] = picked
         s = self.settings
         flags = (RT_DISPLAY_TONEMAP if s.enable_tone_mapping else 0) | \
                 (RT_DISPLAY_GAMMA if s.enable_tone_mapping and s.enable_gamma_correction else 0)
@@ -248,6 +252,21 @@ class Session:
             self.r.tonemap_async(slot, flags)
         self._queued.append((out, slot))
         return self._fetch_oldest() if len(self._queued) >= self.in_flight else None
+
+    def _pick(self, fp: FrameParams, xpos: float, ypos: float) -> dict:
+        """What is under the cursor, with the frame's own uniforms and before the frame is queued:
+        window coordinates (GLFW: origin top-left) -> the accumulation's pixel (row 0 = bottom),
+        rt_pick, and the material of the picked triangle for an editor (feed it back through
+        Input.materials = [(triangle, 1, material)])."""
+        px, py = int(np.floor(xpos)), self.height - 1 - int(np.floor(ypos))
+        h = self.r.pick(fp, px, py)
+        tri = int(h["triangle"])
+        out = {"pixel": (px, py), "triangle": tri, "material_id": int(h["material"]) if tri >= 0 else -1,
+               "t": float(h["t"]), "point": np.array(h["point"], f32), "normal": np.array(h["normal"], f32),
+               "inside": bool(h["inside"]), "material": None}
+        if tri >= 0:
+            out["material"] = sl.Material.from_texels(self.r.triangle_material(tri)[0])
+        return out
 
     def _fetch_oldest(self) -> dict:
         out, slot = self._queued.pop(0)

@@ -26,9 +26,12 @@ RT_FLAG_NO_FINISH = 8
 RT_FLAG_FINISH = 16
 RT_FLAG_SERIAL = 32
 RT_FLAG_SORTED_TRAVERSAL = 64
-RT_ABI_VERSION = 6
+RT_ABI_VERSION = 7
 RT_GATHER_AUTO, RT_GATHER_RCCL, RT_GATHER_PEER = 0, 1, 2
 RT_LAYOUT_FRAME, RT_LAYOUT_LOCAL_TILES = 0, 1
+RT_HIT_INVALID = -2
+RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1
+RT_QUERY_NO_CULL = 1
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -43,12 +46,29 @@ ABI_SYMBOLS = (
     "rt_tile_costs", "rt_set_finish", "rt_order_work", "rt_set_pipeline",
     "rt_tonemap_async", "rt_display_fetch", "rt_stats_get_sized", "rt_abi_version", "rt_gather_ex",
     "rt_gather_last_transport",
+    "rt_trace_rays", "rt_trace_rays_device", "rt_camera_rays", "rt_first_hit", "rt_first_hit_device", "rt_pick",
+    "rt_get_triangle_material",
 )
 RT_DISPLAY_TONEMAP, RT_DISPLAY_GAMMA = 1, 2
 
 
 class RtMaterial(C.Structure):
     _fields_ = [("v", C.c_float * 24)]
+
+
+class RtRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+class RtHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("inside", C.c_int32),
+                ("triangle", C.c_int32), ("material", C.c_int32), ("pad_", C.c_int32 * 2)]
+
+
+# the same records as numpy dtypes (trace_rays, camera_rays, first_hit)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("dir", np.float32, 3)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("inside", np.int32),
+                      ("triangle", np.int32), ("material", np.int32), ("pad_", np.int32, 2)])
 
 
 class RtSceneSoa(C.Structure):
@@ -213,6 +233,15 @@ def _bind(L: C.CDLL) -> C.CDLL:
     if hasattr(L, "rt_gather_ex"):
         L.rt_gather_ex.argtypes = [C.POINTER(vp), C.c_int32, _f32p, C.c_int32]
         L.rt_gather_last_transport.argtypes = [vp]
+    if hasattr(L, "rt_trace_rays"):  # ABI >= 7
+        fpp = C.POINTER(RtFrameParams)
+        L.rt_trace_rays.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
+        L.rt_trace_rays_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_float, vp]
+        L.rt_camera_rays.argtypes = [vp, fpp, vp, C.c_int32]
+        L.rt_first_hit.argtypes = [vp, fpp, vp, C.c_int32]
+        L.rt_first_hit_device.argtypes = [vp, fpp, vp]
+        L.rt_pick.argtypes = [vp, fpp, C.c_int32, C.c_int32, C.POINTER(RtHit)]
+        L.rt_get_triangle_material.argtypes = [vp, C.c_int32, C.POINTER(RtMaterial), _i32p]
     return L
 
 
@@ -467,3 +496,62 @@ class Renderer:
         self._check(self._L.rt_display_fetch(self._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_uint8))),
                     "rt_display_fetch")
         return out
+
+    # ------------------------------------------------------------- ray queries
+    def trace_rays(self, origins, dirs, kind: str = "closest", no_cull: bool = False) -> np.ndarray:
+        """rt_trace_rays: hitBVH for rays (origins[i], dirs[i]), both (n, 3).  kind "closest": a
+        structured array of HIT_DTYPE (a miss has triangle -1 and t -1, an untraced ray triangle
+        RT_HIT_INVALID); kind "any": int32 per ray, 1 occluded, 0 not, RT_HIT_INVALID untraced."""
+        kinds = {"closest": RT_QUERY_CLOSEST, "any": RT_QUERY_ANY}
+        k = kinds[kind] if kind in kinds else int(kind)  # (an unknown kind reaches the library: RT_ERR_ARG)
+        rays = np.zeros(len(origins), RAY_DTYPE)
+        rays["origin"] = np.asarray(origins, np.float32).reshape(-1, 3)
+        rays["dir"] = np.asarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros(len(rays), np.int32 if k == RT_QUERY_ANY else HIT_DTYPE)
+        self._check(self._L.rt_trace_rays(self._h, rays.ctypes.data, len(rays), k,
+                                          RT_QUERY_NO_CULL if no_cull else 0, out.ctypes.data), "rt_trace_rays")
+        return out
+
+    def trace_rays_device(self, rays_ptr: int, n: int, out_ptr: int, origin_bound: float, kind: str = "closest",
+                          no_cull: bool = False) -> None:
+        """rt_trace_rays_device: n rt_ray records at device pointer rays_ptr -> rt_hit / int32 records
+        at out_ptr, enqueued on the ctx stream (valid after synchronize())."""
+        k = {"closest": RT_QUERY_CLOSEST, "any": RT_QUERY_ANY}[kind]
+        self._check(self._L.rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), int(n), k,
+                                                 RT_QUERY_NO_CULL if no_cull else 0, float(origin_bound),
+                                                 C.c_void_p(out_ptr)), "rt_trace_rays_device")
+
+    def camera_rays(self, params: FrameParams) -> np.ndarray:
+        """(H, W) RAY_DTYPE, row 0 = bottom row: the camera rays of this rank's pixels as the render
+        computes them (other ranks' pixels are 0)."""
+        out = np.zeros((self.height, self.width), RAY_DTYPE)
+        p = params.to_c()
+        self._check(self._L.rt_camera_rays(self._h, C.byref(p), out.ctypes.data, RT_LAYOUT_FRAME), "rt_camera_rays")
+        return out
+
+    def first_hit(self, params: FrameParams) -> np.ndarray:
+        """(H, W) HIT_DTYPE, row 0 = bottom row: the closest hit of every camera ray of this rank
+        (other ranks' pixels are 0)."""
+        out = np.zeros((self.height, self.width), HIT_DTYPE)
+        p = params.to_c()
+        self._check(self._L.rt_first_hit(self._h, C.byref(p), out.ctypes.data, RT_LAYOUT_FRAME), "rt_first_hit")
+        return out
+
+    def first_hit_device(self, params: FrameParams, hits_ptr: int) -> None:
+        """rt_first_hit_device: the first-hit frame in local-tile order at device pointer hits_ptr."""
+        p = params.to_c()
+        self._check(self._L.rt_first_hit_device(self._h, C.byref(p), C.c_void_p(hits_ptr)), "rt_first_hit_device")
+
+    def pick(self, params: FrameParams, px: int, py: int) -> np.ndarray:
+        """The hit of pixel (px, py)'s camera ray (row 0 = bottom): one HIT_DTYPE record."""
+        h = RtHit()
+        p = params.to_c()
+        self._check(self._L.rt_pick(self._h, C.byref(p), int(px), int(py), C.byref(h)), "rt_pick")
+        return np.frombuffer(bytes(h), HIT_DTYPE)[0]
+
+    def triangle_material(self, triangle: int):
+        """(the 24 material floats of a post-BVH triangle, its material-table index)"""
+        m, mid = RtMaterial(), C.c_int32()
+        self._check(self._L.rt_get_triangle_material(self._h, int(triangle), C.byref(m), C.byref(mid)),
+                    "rt_get_triangle_material")
+        return np.array(m.v, np.float32), mid.value

@@ -74,6 +74,12 @@ class Material:
             self.ior, self.transmission] + list(self.medium_color) + [
             self.medium_type, self.medium_density, self.medium_anisotropy], dtype=np.float32)
 
+    @classmethod
+    def from_texels(cls, t) -> "Material":
+        """The inverse of texels(): a Material from its 24 floats (rt_get_triangle_material)."""
+        t = [float(x) for x in np.asarray(t, np.float32).reshape(24)]
+        return cls(tuple(t[0:3]), tuple(t[3:6]), *t[6:18], tuple(t[18:21]), *t[21:24])
+
 
 _lib = None
 
