@@ -127,6 +127,32 @@ int rts_glibc_rand(unsigned int seed, int n, int* out);
  * reference's edge functions alone.  For tests: it replaces no reference interface. */
 int rts_tri_filter(const float* tri, int n_triangles, float* out, double* k, int32_t* flagged);
 
+/* The HIP path's scene compiler (csrc/common/scene_compile.h; rt_set_scene uploads what the same
+ * code returns): an rt_scene_soa (rt_abi.h), or the reference's encodings, -> the device arrays
+ * and scalars.  A test and tooling interface: it replaces no reference interface.  options = four
+ * int32 {rebuild, greedy, bfs, wide} (scn::Options), NULL for the defaults.  Both compile calls
+ * return rt_set_scene's code for the scene (RT_OK, RT_ERR_ARG, RT_ERR_LIMIT) and leave *out
+ * allocated (release with rts_compiled_free) unless they return for a null argument or no memory;
+ * after a rejection the view's arrays are empty and err says why.  The view's pointers live as
+ * long as the handle; the counts are in floats (tri, trx, trin, hrec, mats), 64-B binary nodes,
+ * 128-B 4-wide nodes and int32 (tri_mat). */
+struct rt_scene_soa;
+typedef struct rts_compiled rts_compiled;
+typedef struct rts_compiled_view {
+  const float *tri, *trx, *trin, *hrec, *mats;
+  const void *nodes, *qnodes;
+  const int32_t* tri_mat;
+  int64_t n_tri_f, n_trx_f, n_trin_f, n_hrec_f, n_mats_f, n_nodes, n_qnodes, n_tri_mat;
+  double cull_R, cull_K, cull_off, tri_k1, tri_k0;
+  int32_t n_tri, n_mats, root, has_scene, depth, qroot, qdepth, wide, tri_flagged;
+  const char* err;
+} rts_compiled_view;
+int rts_compile_scene(const struct rt_scene_soa* scene, const int32_t* options, rts_compiled** out);
+int rts_compile_scene_encoded(const float* tri_enc, int32_t n_triangles, const float* node_enc, int32_t n_nodes,
+                              const int32_t* options, rts_compiled** out);
+int rts_compiled_get(const rts_compiled* k, rts_compiled_view* view);
+void rts_compiled_free(rts_compiled* k);
+
 /* 8-bit RGB PNG (stbi_write_png in SaveFrame, src/core/Utility.h:19-30): width*height*3 bytes,
  * row 0 = top (rt_tonemap's output order).  Stored (uncompressed) deflate, no zlib needed. */
 int rts_write_png(const char* path, int width, int height, const uint8_t* rgb);

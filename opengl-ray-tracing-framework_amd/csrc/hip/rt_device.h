@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "glsl_math.h"
+#include "scene_compile.h"
 
 #pragma clang fp contract(off)
 
@@ -80,11 +81,12 @@ struct __attribute__((aligned(16))) QNode {
   int4 pad;
 };
 static_assert(sizeof(QNode) == 128, "one cache line");
-constexpr int Q_EMPTY = 0x7fffffff;
-constexpr uint32_t LEAF_BIT = 0x80000000u;
-RTD bool ref_is_leaf(int r) { return ((uint32_t)r & LEAF_BIT) != 0u; }
-RTD int leaf_first(int r) { return (int)(((uint32_t)r & 0x7fffffffu) >> 4); }
-RTD int leaf_count(int r) { return (int)((uint32_t)r & 15u) + 1; }
+// the child references, as the scene compiler writes them (scene_compile.h)
+using scn::Q_EMPTY;
+using scn::LEAF_BIT;
+RTD bool ref_is_leaf(int r) { return scn::ref_is_leaf(r); }
+RTD int leaf_first(int r) { return scn::leaf_first(r); }
+RTD int leaf_count(int r) { return scn::leaf_count(r); }
 
 // Material table entry: 32 floats (the 24 Material.h floats, then ax, ay precomputed by
 // getMaterial's formula RT:205-207, then the int medium type).

@@ -89,7 +89,7 @@ RTD float slab(f3 o, f3 inv, f3 AA, f3 BB, float& t0_out) {
 
 // Culling bound: a popped subtree whose box entry lies beyond this can hold no hit the reference
 // would accept at dist <= best.  Accepted hit points lie within P.cull_eps of their triangle's
-// boxes (cull_bound_stats in rt_render.hip), so a triangle's t is at least t0 - cull_eps *
+// boxes (cull_bound_stats in scene_compile.h), so a triangle's t is at least t0 - cull_eps *
 // max|1/d_a|; the 1e-3 terms cover the relative rounding of t0, t and dist = t - 1e-5.  A ray with
 // a zero direction component (1/d infinite) is never culled.
 RTD float cull_limit(float best, float eps, float ix, float iy, float iz) {

@@ -1,7 +1,7 @@
 // rt_render.hip — librtamd.so: the C-ABI of include/rt_abi.h over the gfx950 path-tracing
-// kernels of rt_kernels.h.  Host code here converts the reference's scene description
-// (SoA or the reference's own AoS encodings) into the device layout, owns the device
-// buffers and launches the persistent kernel.  No fallback path: without a HIP device every
+// kernels of rt_kernels.h.  Host code here uploads what the scene compiler
+// (csrc/common/scene_compile.h) makes of the reference's scene description (SoA or the
+// reference's own AoS encodings), owns the device buffers and launches the persistent kernel.  No fallback path: without a HIP device every
 // entry point returns RT_ERR_NODEVICE / RT_ERR_HIP.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -11,7 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
+#include <cstddef>
 #include <new>
 #include <string>
 #include <vector>
@@ -32,7 +32,7 @@
 #ifndef RT_SPLIT_CONT_FIRST  // split queues: the continuations' launch first (1) or the shadow rays' (0)
 #define RT_SPLIT_CONT_FIRST 0  // C3 1 vs 0: -0.16% (profiles/r06_ab_split_knobs_C3.log)
 #endif
-#include "tri_filter.h"
+#include "scene_compile.h"
 
 using rtd::GNode;
 using rtd::KParams;
@@ -250,364 +250,25 @@ void dfree(T*& p) {
   p = nullptr;
 }
 
-// Same fp32 operations as the shader's per-test N = normalize(cross(p2-p1, p3-p1)) (RT:253).
-inline void geometric_normal(const float* p1, const float* p2, const float* p3, float* n) {
-  float ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
-  float bx = p3[0] - p1[0], by = p3[1] - p1[1], bz = p3[2] - p1[2];
-  float cx = ay * bz - by * az, cy = az * bx - bz * ax, cz = ax * by - bx * ay;
-  float inv = 1.0f / sqrtf(cx * cx + cy * cy + cz * cz);
-  n[0] = cx * inv; n[1] = cy * inv; n[2] = cz * inv;
-}
+// The scene compiler's records are uploaded as the device's (scene_compile.h, rt_device.h)
+static_assert(sizeof(scn::BNode) == sizeof(GNode) && offsetof(scn::BNode, box) == offsetof(GNode, b0) &&
+              offsetof(scn::BNode, box[4]) == offsetof(GNode, b1) && offsetof(scn::BNode, box[8]) == offsetof(GNode, b2) &&
+              offsetof(scn::BNode, ref) == offsetof(GNode, ref), "scn::BNode is rtd::GNode");
+static_assert(sizeof(scn::WNode) == sizeof(rtd::QNode) && offsetof(scn::WNode, lo) == offsetof(rtd::QNode, lox) &&
+              offsetof(scn::WNode, lo[1]) == offsetof(rtd::QNode, loy) && offsetof(scn::WNode, lo[2]) == offsetof(rtd::QNode, loz) &&
+              offsetof(scn::WNode, hi) == offsetof(rtd::QNode, hix) && offsetof(scn::WNode, hi[1]) == offsetof(rtd::QNode, hiy) &&
+              offsetof(scn::WNode, hi[2]) == offsetof(rtd::QNode, hiz) && offsetof(scn::WNode, ref) == offsetof(rtd::QNode, ref) &&
+              offsetof(scn::WNode, pad) == offsetof(rtd::QNode, pad), "scn::WNode is rtd::QNode");
 
-// Culling bound ("What the culling margin covers").  A subtree may be skipped when
-// its box entry t0 exceeds the best hit; that is exact only if no triangle inside the box can be
-// accepted by the reference's test (RT:241-299) at a computed t below t0.  An accepted hit point
-// P = S + d*t (fp32) lies within eps (per axis) of its triangle, hence of every box holding it:
-//   off-plane |(P - p1).N| <= 36 u R  (rounding of RT:265 and of P; R bounds |coords|, origins),
-//   in-plane slack of the three edge signs <= 70 u R / cos(theta)  (theta: fp32 N vs exact normal),
-//   X = S + d*t (exact) vs P: <= 8 u R,
-//   + the triangle's vertices off the plane (p1, N): max_k |(pk - p1).N|,
-// so t >= t0 - eps * max|1/d_a|.  Returned per scene: K (units of u R) and off; the render
-// doubles eps = K u R + off as safety.  Degenerate (zero-area with a finite fp32 normal) or badly
-// conditioned triangles, or triangles outside their leaf box, give K = inf: no culling.
-struct CullStats {
-  double R = 0.0, K = 0.0, off = 0.0;
-};
-CullStats cull_bound_stats(const rt_scene_soa* s) {
-  CullStats cs;
-  const int nt = s->n_triangles;
-  for (int i = 0; i < nt; i++) {
-    const float* p[3] = {s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i};
-    float ng[3];
-    geometric_normal(p[0], p[1], p[2], ng);
-    for (int k = 0; k < 3; k++)
-      for (int a = 0; a < 3; a++) cs.R = std::max(cs.R, std::fabs((double)p[k][a]));
-    if (!(std::isfinite(ng[0]) && std::isfinite(ng[1]) && std::isfinite(ng[2]))) continue;  // never hit (NaN tests)
-    double e1[3], e2[3], cx[3];
-    for (int a = 0; a < 3; a++) { e1[a] = (double)p[1][a] - p[0][a]; e2[a] = (double)p[2][a] - p[0][a]; }
-    cx[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    cx[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    cx[2] = e1[0] * e2[1] - e1[1] * e2[0];
-    const double nrm = std::sqrt(cx[0] * cx[0] + cx[1] * cx[1] + cx[2] * cx[2]);
-    const double cosT = nrm > 0.0 ? (ng[0] * cx[0] + ng[1] * cx[1] + ng[2] * cx[2]) / nrm : 0.0;
-    if (!(cosT > 0.25)) { cs.K = INFINITY; continue; }
-    cs.K = std::max(cs.K, 44.0 + 70.0 / cosT);
-    for (int k = 1; k < 3; k++) {
-      double o = 0.0;
-      for (int a = 0; a < 3; a++) o += ((double)p[k][a] - p[0][a]) * ng[a];
-      cs.off = std::max(cs.off, std::fabs(o));
-    }
-  }
-  // every leaf's triangles inside the leaf's box (the reference's own boxes are their min/max)
-  for (int n = 1; n < s->n_nodes && s->node_n; n++) {
-    if (s->node_n[n] <= 0) continue;
-    for (int i = s->node_index[n]; i < s->node_index[n] + s->node_n[n] && i < nt; i++)
-      for (const float* q : {s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i})
-        for (int a = 0; a < 3; a++)
-          if (!(q[a] >= s->node_aa[3 * n + a] && q[a] <= s->node_bb[3 * n + a])) cs.K = INFINITY;
-  }
-  return cs;
-}
-
-// Material.h fields -> 32-float device entry; ax/ay by getMaterial's formula (RT:205-207).
-void pack_material(const rt_material& m, float* o) {
-  const float* f = reinterpret_cast<const float*>(&m);
-  for (int k = 0; k < 24; k++) o[k] = f[k];
-  float aspect = gm::sqrt_(1.0f - m.anisotropic * 0.9f);
-  o[24] = gm::max_(0.001f, (m.roughness * m.roughness) / aspect);
-  o[25] = gm::max_(0.001f, (m.roughness * m.roughness) * aspect);
-  int mt = (int)m.medium_type;
-  memcpy(&o[26], &mt, 4);
-  o[27] = o[28] = o[29] = o[30] = o[31] = 0.0f;
-}
-
-// New internal levels over the reference's leaves.  A leaf keeps its triangle range and its exact
-// box (the reference's, RT:363-368); every internal box is the exact min/max union of the boxes
-// below it.  The slab arithmetic is monotone in the box planes, so a box can only be hit when
-// every box above it is: the traversal reaches exactly the leaves whose own box the reference's
-// ray hits, whatever the internal levels are (the reference's exact-tie order is kept separately,
-// by the leaf ranks of its own tree).  The reference's top levels are X-median splits (R18: SAH
-// costs above INF = 114514 fall back to the median), so a full-sweep SAH over the leaf boxes
-// (centroid order per axis, cost = area x triangles) gives a tree with fewer node visits.
-// Returns the root of `out` (binary GNodes, host only: the device keeps the reference tree).
-int rebuild_over_leaves(const std::vector<GNode>& gn, int root, std::vector<GNode>& out) {
-  struct Box {
-    float lo[3], hi[3];
-  };
-  struct Prim {
-    int ref, n;
-    Box b;
-    double c[3];
-  };
-  auto is_leaf = [](int r) { return ((uint32_t)r & rtd::LEAF_BIT) != 0u; };
-  std::vector<Prim> prims;
-  std::vector<int> st{root};
-  while (!st.empty()) {
-    const GNode g = gn[st.back()];
-    st.pop_back();
-    const Box bl = {{g.b0.x, g.b0.y, g.b0.z}, {g.b0.w, g.b1.x, g.b1.y}};
-    const Box br = {{g.b1.z, g.b1.w, g.b2.x}, {g.b2.y, g.b2.z, g.b2.w}};
-    const int refs[2] = {g.ref.x, g.ref.y};
-    const Box* boxes[2] = {&bl, &br};
-    for (int k = 0; k < 2; k++) {
-      if (!is_leaf(refs[k])) { st.push_back(refs[k]); continue; }
-      Prim p;
-      p.ref = refs[k];
-      p.n = (int)((uint32_t)refs[k] & 15u) + 1;      p.b = *boxes[k];
-      for (int a = 0; a < 3; a++) p.c[a] = 0.5 * ((double)p.b.lo[a] + (double)p.b.hi[a]);
-      prims.push_back(p);
-    }
-  }
-  auto unite = [](const Box& a, const Box& b) {
-    Box u;
-    for (int k = 0; k < 3; k++) { u.lo[k] = std::min(a.lo[k], b.lo[k]); u.hi[k] = std::max(a.hi[k], b.hi[k]); }
-    return u;
-  };
-  auto area = [](const Box& b) {
-    double e[3];
-    for (int k = 0; k < 3; k++) e[k] = std::max(0.0, (double)b.hi[k] - (double)b.lo[k]);
-    return e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
-  };
-  std::vector<int> idx(prims.size()), tmp(prims.size());
-  for (size_t i = 0; i < idx.size(); i++) idx[i] = (int)i;
-  std::vector<double> right_cost(prims.size() + 1);
-  out.clear();
-  out.reserve(prims.size());
-  std::function<int(int, int, Box&)> rec = [&](int b, int e, Box& box) -> int {
-    if (e - b == 1) {
-      box = prims[idx[b]].b;
-      return prims[idx[b]].ref;
-    }
-    double best = 1e300;
-    int bax = 0, bpos = b + (e - b) / 2;
-    for (int ax = 0; ax < 3; ax++) {
-      std::copy(idx.begin() + b, idx.begin() + e, tmp.begin() + b);
-      std::sort(tmp.begin() + b, tmp.begin() + e, [&](int x, int y) {
-        return prims[x].c[ax] < prims[y].c[ax] || (prims[x].c[ax] == prims[y].c[ax] && x < y);
-      });
-      Box acc = prims[tmp[e - 1]].b;
-      int cnt = 0;
-      for (int i = e - 1; i > b; i--) {  // right_cost[i] = cost of [i, e)
-        acc = unite(acc, prims[tmp[i]].b);
-        cnt += prims[tmp[i]].n;
-        right_cost[i - b] = area(acc) * cnt;
-      }
-      acc = prims[tmp[b]].b;
-      cnt = 0;
-      for (int i = b; i < e - 1; i++) {  // split after i: [b, i] | [i + 1, e)
-        acc = unite(acc, prims[tmp[i]].b);
-        cnt += prims[tmp[i]].n;
-        const double c = area(acc) * cnt + right_cost[i + 1 - b];
-        if (c < best) { best = c; bax = ax; bpos = i + 1; }
-      }
-    }
-    std::sort(idx.begin() + b, idx.begin() + e, [&](int x, int y) {
-      return prims[x].c[bax] < prims[y].c[bax] || (prims[x].c[bax] == prims[y].c[bax] && x < y);
-    });
-    const int me = (int)out.size();
-    out.push_back(GNode{});
-    Box lb, rb;
-    const int lr = rec(b, bpos, lb), rr = rec(bpos, e, rb);
-    GNode g;
-    memset(&g, 0, sizeof(g));
-    g.b0 = make_float4(lb.lo[0], lb.lo[1], lb.lo[2], lb.hi[0]);
-    g.b1 = make_float4(lb.hi[1], lb.hi[2], rb.lo[0], rb.lo[1]);
-    g.b2 = make_float4(rb.lo[2], rb.hi[0], rb.hi[1], rb.hi[2]);
-    g.ref = make_int4(lr, rr, 0, 0);
-    out[me] = g;
-    box = unite(lb, rb);
-    return me;
-  };
-  Box rootbox;
-  return rec(0, (int)prims.size(), rootbox);
-}
-
-// Leaf ranks + 4-wide collapse of the binary tree.
-// * Leaf rank = position of the leaf in the reference's left-first DFS; gn[k].ref.z = rank of
-//   the first leaf of node k's right subtree; trin[3t+1].w = rank of triangle t's leaf.  These
-//   let the 4-wide traversal break exact distance ties the way the reference's visit order does.
-// * A QNode replaces a binary node and a cut of its subtree with at most 4 slots, chosen by the
-//   SAH-optimal collapse below (or greedily, largest area first).  Boxes are copied bit for bit.  A (grand)child box can only be hit when every box above it is
-//   (children are min/max over subsets, and the slab arithmetic is monotone), so the 4-wide
-//   traversal reaches exactly the reference's leaves.
-// Returns false (binary traversal only) when a triangle belongs to two leaves.
-bool build_wide(std::vector<GNode>& gn, int root, std::vector<float4>& trin, std::vector<rtd::QNode>& qn,
-                int& qroot, int& qdepth) {
-  const int nt = (int)(trin.size() / 3);
-  auto is_leaf = [](int r) { return ((uint32_t)r & rtd::LEAF_BIT) != 0u; };
-  auto first_of = [](int r) { return (int)(((uint32_t)r & 0x7fffffffu) >> 4); };
-  auto count_of = [](int r) { return (int)((uint32_t)r & 15u) + 1; };
-  std::vector<int> tri_rank(nt, -1);
-  int rank = 0;
-  bool ok = true;
-  std::function<void(int)> rank_dfs = [&](int r) {
-    if (is_leaf(r)) {
-      for (int t = first_of(r); t < first_of(r) + count_of(r); t++) {
-        if (tri_rank[t] >= 0) ok = false;
-        tri_rank[t] = rank;
-      }
-      rank++;
-      return;
-    }
-    rank_dfs(gn[r].ref.x);
-    gn[r].ref.z = rank;
-    rank_dfs(gn[r].ref.y);
-  };
-  rank_dfs(root);
-  for (int t = 0; t < nt; t++) {
-    float w;
-    memcpy(&w, &tri_rank[t], 4);
-    trin[3 * t + 1].w = w;
-  }
-  if (!ok) return false;
-  // The tree that gets collapsed: by default internal levels rebuilt over the reference's leaves
-  // (rebuild_over_leaves), RT_REBUILD=0 keeps the reference's own internal nodes.
-  std::vector<GNode> rebuilt;
-  int croot = root;
-  const std::vector<GNode>* T = &gn;
-  const char* re = knob("RT_REBUILD");
-  if (!is_leaf(root) && !(re && atoi(re) == 0)) {
-    croot = rebuild_over_leaves(gn, root, rebuilt);
-    T = &rebuilt;
-  }
-  struct Slot {
-    int ref;
-    float lo[3], hi[3];
-  };
-  auto kids = [&](int b, Slot& L, Slot& R) {
-    const GNode& g = (*T)[b];
-    L = Slot{g.ref.x, {g.b0.x, g.b0.y, g.b0.z}, {g.b0.w, g.b1.x, g.b1.y}};
-    R = Slot{g.ref.y, {g.b1.z, g.b1.w, g.b2.x}, {g.b2.y, g.b2.z, g.b2.w}};
-  };
-  auto area = [](const Slot& s) {
-    double e[3];
-    for (int k = 0; k < 3; k++) e[k] = (double)s.hi[k] - (double)s.lo[k];
-    return e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
-  };
-  // Which binary nodes become 4-wide nodes.  Default: the collapse that minimises the summed
-  // surface area of the 4-wide nodes (the SAH traversal cost; the leaves and their cost are
-  // fixed): f(n, k) = least area of 4-wide roots covering n's subtree with at most k slots,
-  // f(n, 1) = A(n) + min_j f(L, j) + f(R, 4 - j), f(n, k) = min(f(n, 1), min_j f(L, j) + f(R, k - j)).
-  // RT_COLLAPSE=greedy: open the largest-area internal slot until there are four.
-  const char* ce = knob("RT_COLLAPSE");
-  const bool greedy = ce && strcmp(ce, "greedy") == 0;
-  const size_t nb = T->size();
-  std::vector<double> f(nb * 5, 0.0);
-  std::vector<signed char> split(nb * 5, 0);  // 0: keep the node as one slot, j > 0: j slots to the left
-  auto fr = [&](int r, int k) -> double { return is_leaf(r) ? 0.0 : f[(size_t)r * 5 + k]; };
-  if (!greedy && !is_leaf(croot)) {
-    std::function<void(int)> dp = [&](int b) {
-      Slot L, R;
-      kids(b, L, R);
-      if (!is_leaf(L.ref)) dp(L.ref);
-      if (!is_leaf(R.ref)) dp(R.ref);
-      Slot U = L;
-      for (int k = 0; k < 3; k++) { U.lo[k] = std::min(L.lo[k], R.lo[k]); U.hi[k] = std::max(L.hi[k], R.hi[k]); }
-      double open = 1e300;
-      int jo = 1;
-      for (int j = 1; j <= 3; j++) {
-        const double c = fr(L.ref, j) + fr(R.ref, 4 - j);
-        if (c < open) { open = c; jo = j; }
-      }
-      f[(size_t)b * 5 + 1] = area(U) + open;
-      split[(size_t)b * 5 + 1] = (signed char)jo;  // the split of the node's own 4-wide record
-      for (int k = 2; k <= 4; k++) {
-        double best = f[(size_t)b * 5 + 1];
-        int bj = 0;
-        for (int j = 1; j < k; j++) {
-          const double c = fr(L.ref, j) + fr(R.ref, k - j);
-          if (c < best) { best = c; bj = j; }
-        }
-        f[(size_t)b * 5 + k] = best;
-        split[(size_t)b * 5 + k] = (signed char)bj;
-      }
-    };
-    dp(croot);
-  }
-  // DP reconstruction: the slots that binary subtree s contributes when given k of them
-  std::function<void(const Slot&, int, std::vector<Slot>&)> collect = [&](const Slot& s, int k, std::vector<Slot>& out) {
-    if (is_leaf(s.ref) || k == 1 || split[(size_t)s.ref * 5 + k] == 0) { out.push_back(s); return; }
-    const int j = split[(size_t)s.ref * 5 + k];
-    Slot L, R;
-    kids(s.ref, L, R);
-    collect(L, j, out);
-    collect(R, k - j, out);
-  };
-  qdepth = 1;
-  std::function<int(int, int)> build = [&](int b, int depth) -> int {
-    qdepth = std::max(qdepth, depth);
-    const int idx = (int)qn.size();
-    qn.push_back(rtd::QNode{});
-    std::vector<Slot> sl;
-    if (greedy) {
-      sl.resize(2);
-      kids(b, sl[0], sl[1]);
-      while (sl.size() < 4) {
-        int pick = -1;
-        double pa = -1.0;
-        for (size_t i = 0; i < sl.size(); i++)
-          if (!is_leaf(sl[i].ref) && area(sl[i]) > pa) { pa = area(sl[i]); pick = (int)i; }
-        if (pick < 0) break;
-        Slot x, y;
-        kids(sl[pick].ref, x, y);
-        sl[pick] = x;
-        sl.insert(sl.begin() + pick + 1, y);
-      }
-    } else {
-      Slot L, R;
-      kids(b, L, R);
-      const int j = split[(size_t)b * 5 + 1];
-      collect(L, j, sl);
-      collect(R, 4 - j, sl);
-    }
-    int refs[4] = {rtd::Q_EMPTY, rtd::Q_EMPTY, rtd::Q_EMPTY, rtd::Q_EMPTY};
-    for (size_t i = 0; i < sl.size(); i++) refs[i] = is_leaf(sl[i].ref) ? sl[i].ref : build(sl[i].ref, depth + 1);
-    // an empty slot is the inverted box lo = +inf, hi = -inf: for a finite 1/d the sign-selected
-    // planes give entry t0 = +inf and exit t1 = -inf, so the slab test never hits it (the literal
-    // slab of a ray with a zero direction component tests the slot's ref instead: its per-axis
-    // min / max would turn the inverted box into an infinite one)
-    const float pinf = INFINITY;
-    float lo[3][4], hi[3][4];
-    for (int k = 0; k < 3; k++)
-      for (int i = 0; i < 4; i++) {
-        lo[k][i] = i < (int)sl.size() ? sl[i].lo[k] : pinf;
-        hi[k][i] = i < (int)sl.size() ? sl[i].hi[k] : -pinf;
-      }
-    rtd::QNode& q = qn[idx];
-    q.lox = make_float4(lo[0][0], lo[0][1], lo[0][2], lo[0][3]);
-    q.loy = make_float4(lo[1][0], lo[1][1], lo[1][2], lo[1][3]);
-    q.loz = make_float4(lo[2][0], lo[2][1], lo[2][2], lo[2][3]);
-    q.hix = make_float4(hi[0][0], hi[0][1], hi[0][2], hi[0][3]);
-    q.hiy = make_float4(hi[1][0], hi[1][1], hi[1][2], hi[1][3]);
-    q.hiz = make_float4(hi[2][0], hi[2][1], hi[2][2], hi[2][3]);
-    q.ref = make_int4(refs[0], refs[1], refs[2], refs[3]);
-    return idx;
-  };
-  qroot = is_leaf(croot) ? croot : build(croot, 1);
-  const char* qb = knob("RT_QBFS");
-  if (!is_leaf(qroot) && !(qb && atoi(qb) == 0)) {
-    // breadth-first numbering (RT_QBFS=0: depth-first): the top levels of the tree are the
-    // first nodes (RT_DEBUG_PASSES reports node visits by this index)
-    std::vector<int> order{qroot}, newid(qn.size(), -1);
-    newid[qroot] = 0;
-    for (size_t h = 0; h < order.size(); h++) {
-      const int4 r = qn[order[h]].ref;
-      for (int x : {r.x, r.y, r.z, r.w})
-        if (x != rtd::Q_EMPTY && !is_leaf(x)) {
-          newid[x] = (int)order.size();
-          order.push_back(x);
-        }
-    }
-    std::vector<rtd::QNode> bq(order.size());
-    auto remap = [&](int x) { return (x == rtd::Q_EMPTY || is_leaf(x)) ? x : newid[x]; };
-    for (size_t i = 0; i < order.size(); i++) {
-      bq[i] = qn[order[i]];
-      bq[i].ref = make_int4(remap(bq[i].ref.x), remap(bq[i].ref.y), remap(bq[i].ref.z), remap(bq[i].ref.w));
-    }
-    qn.swap(bq);
-    qroot = 0;
-  }
-  return true;
+// The traversal-structure variants the parity tests cover (development builds; the release
+// library compiles every scene with the defaults)
+scn::Options scene_options() {
+  scn::Options o;
+  if (const char* e = knob("RT_REBUILD")) o.rebuild = atoi(e) != 0;
+  if (const char* e = knob("RT_COLLAPSE")) o.greedy = strcmp(e, "greedy") == 0;
+  if (const char* e = knob("RT_QBFS")) o.bfs = atoi(e) != 0;
+  if (const char* e = knob("RT_BVH_WIDTH")) o.wide = atoi(e) != 2;
+  return o;
 }
 
 int upload(rt_ctx* c, void** dst, const void* src, size_t bytes) {
@@ -1018,183 +679,48 @@ int rt_device_info(const rt_ctx* c, int32_t* n_cus, int32_t* blocks_per_cu, int3
   return RT_OK;
 }
 
+
 int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   if (!c || !s) return RT_ERR_ARG;
-  if (s->n_triangles < 0 || s->n_nodes < 0 || s->n_materials < 0) return fail(c, RT_ERR_ARG, "negative count");
-  const int nt = s->n_triangles;
-  if (nt > 0 && (!s->p1 || !s->p2 || !s->p3 || !s->n1 || !s->n2 || !s->n3 || !s->material_id || !s->materials))
-    return fail(c, RT_ERR_ARG, "missing triangle arrays");
-  if (nt >= (1 << 27)) return fail(c, RT_ERR_LIMIT, "more than 2^27 triangles");
+  // a rejected scene touches neither the device nor the context
+  scn::Compiled k;
+  std::string why;
+  if (int rc = scn::compile(s, scene_options(), k, why)) return fail(c, rc, why);
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = drain(c)) return rc;
-  for (int i = 0; i < nt; i++)
-    if (s->material_id[i] < 0 || s->material_id[i] >= s->n_materials)
-      return fail(c, RT_ERR_ARG, "material_id out of range");
-  // ---- triangles
-  std::vector<float4> tri(3 * (size_t)nt), trin(3 * (size_t)nt);
-  for (int i = 0; i < nt; i++) {
-    float ng[3];
-    geometric_normal(s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i, ng);
-    const float* ps[3] = {s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i};
-    const float* ns[3] = {s->n1 + 3 * i, s->n2 + 3 * i, s->n3 + 3 * i};
-    for (int k = 0; k < 3; k++) {
-      tri[3 * i + k] = make_float4(ps[k][0], ps[k][1], ps[k][2], ng[k]);
-      float w = 0.0f;
-      if (k == 0) memcpy(&w, &s->material_id[i], 4);
-      trin[3 * i + k] = make_float4(ns[k][0], ns[k][1], ns[k][2], w);
-    }
-  }
-  // ---- materials
-  std::vector<float> mt(32 * (size_t)std::max(1, s->n_materials), 0.0f);
-  for (int m = 0; m < s->n_materials; m++) pack_material(s->materials[m], &mt[32 * m]);
-  // ---- BVH: reference numbering -> children-in-parent nodes
-  int root = 0, has = 0, depth = 1;
-  std::vector<GNode> gn;
-  if (nt > 0 && s->n_nodes > 1) {
-    if (!s->node_left || !s->node_right || !s->node_n || !s->node_index || !s->node_aa || !s->node_bb)
-      return fail(c, RT_ERR_ARG, "missing node arrays");
-    const int nn = s->n_nodes;
-    std::vector<int> internal_id(nn, -1);
-    auto is_leaf = [&](int i) { return s->node_n[i] > 0; };
-    auto leaf_ref = [&](int i, int& ref) -> int {
-      int n = s->node_n[i], first = s->node_index[i];
-      if (n > 16) return fail(c, RT_ERR_LIMIT, "leaf with more than 16 triangles");
-      if (first < 0 || first + n > nt) return fail(c, RT_ERR_ARG, "leaf range outside the triangle list");
-      ref = (int)(rtd::LEAF_BIT | ((uint32_t)first << 4) | (uint32_t)(n - 1));
-      return RT_OK;
-    };
-    // DFS from the root (node 1) assigning internal ids, checking structure and depth
-    std::vector<std::pair<int, int>> st;
-    st.push_back({1, 1});
-    std::vector<int> order;
-    while (!st.empty()) {
-      auto e = st.back();
-      st.pop_back();
-      int i = e.first;
-      if (i <= 0 || i >= nn) return fail(c, RT_ERR_ARG, "child index out of range");
-      depth = std::max(depth, e.second);
-      if (depth > 64) return fail(c, RT_ERR_LIMIT, "BVH deeper than 64 levels");
-      if (is_leaf(i)) continue;
-      if (internal_id[i] >= 0) return fail(c, RT_ERR_ARG, "BVH is not a tree");
-      if (s->node_left[i] <= 0 || s->node_right[i] <= 0) return fail(c, RT_ERR_ARG, "internal node without two children");
-      internal_id[i] = (int)order.size();
-      order.push_back(i);
-      st.push_back({s->node_right[i], e.second + 1});
-      st.push_back({s->node_left[i], e.second + 1});
-    }
-    gn.resize(std::max<size_t>(1, order.size()));
-    for (size_t k = 0; k < order.size(); k++) {
-      int i = order[k];
-      int l = s->node_left[i], r = s->node_right[i];
-      const float* la = s->node_aa + 3 * l; const float* lb = s->node_bb + 3 * l;
-      const float* ra = s->node_aa + 3 * r; const float* rb = s->node_bb + 3 * r;
-      GNode g;
-      g.b0 = make_float4(la[0], la[1], la[2], lb[0]);
-      g.b1 = make_float4(lb[1], lb[2], ra[0], ra[1]);
-      g.b2 = make_float4(ra[2], rb[0], rb[1], rb[2]);
-      int lr, rr;
-      int rc;
-      if (is_leaf(l)) { if ((rc = leaf_ref(l, lr))) return rc; } else lr = internal_id[l];
-      if (is_leaf(r)) { if ((rc = leaf_ref(r, rr))) return rc; } else rr = internal_id[r];
-      g.ref = make_int4(lr, rr, 0, 0);
-      gn[k] = g;
-    }
-    if (is_leaf(1)) {
-      int rc = leaf_ref(1, root);
-      if (rc) return rc;
-    } else {
-      root = internal_id[1];
-    }
-    has = 1;
-  }
-  std::vector<rtd::QNode> qn;
-  int qroot = root, qdepth = 1;
-  bool wide = false;
-  if (has) wide = build_wide(gn, root, trin, qn, qroot, qdepth);
-  if (const char* e = knob("RT_BVH_WIDTH")) if (atoi(e) == 2) wide = false;
-  if (gn.empty()) {
-    GNode z;
-    memset(&z, 0, sizeof(z));
-    gn.push_back(z);
-  }
-  if (qn.empty()) qn.push_back(rtd::QNode{});
+  // the old buffers no longer describe a scene from here on: a failure below leaves the context
+  // without one (renders and queries then refuse) rather than with a mix of old and new buffers
+  c->scene_set = false;
   int rc;
-  if ((rc = upload(c, (void**)&c->d_qnodes, qn.data(), qn.size() * sizeof(rtd::QNode)))) return rc;
-  c->n_qnodes = (int)qn.size();
-  if ((rc = upload(c, (void**)&c->d_nodes, gn.data(), gn.size() * sizeof(GNode)))) return rc;
-  if ((rc = upload(c, (void**)&c->d_tri, tri.data(), tri.size() * sizeof(float4)))) return rc;
-  {  // traversal records: {p1, Ng.x} {R2, Ng.y} {R3, Ng.z} and the edge filter's margin
-    std::vector<float4> trx(std::max<size_t>(3, tri.size()));
-    const trif::Consts k = trif::build(reinterpret_cast<const float*>(tri.data()), nt, reinterpret_cast<float*>(trx.data()));
-    if ((rc = upload(c, (void**)&c->d_trx, trx.data(), trx.size() * sizeof(float4)))) return rc;
-    c->tri_k1 = k.k1; c->tri_k0 = k.k0; c->tri_flagged = k.flagged;
-  }
-  if ((rc = upload(c, (void**)&c->d_trin, trin.data(), trin.size() * sizeof(float4)))) return rc;
-  {  // hit records: tri's three texels then trin's, one 128-B line per triangle
-    std::vector<float4> hr(8 * std::max<size_t>(1, (size_t)nt), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (size_t i = 0; i < (size_t)nt; i++)
-      for (int k = 0; k < 3; k++) {
-        hr[8 * i + k] = tri[3 * i + k];
-        hr[8 * i + 3 + k] = trin[3 * i + k];
-      }
-    if ((rc = upload(c, (void**)&c->d_hrec, hr.data(), hr.size() * sizeof(float4)))) return rc;
-  }
-  if ((rc = upload(c, (void**)&c->d_mats, mt.data(), mt.size() * sizeof(float)))) return rc;
-  c->n_tri = nt;
-  c->n_mats = s->n_materials;
-  c->root = root;
-  c->has_scene = has;
-  {
-    const CullStats cs = cull_bound_stats(s);
-    c->cull_R = cs.R; c->cull_K = cs.K; c->cull_off = cs.off;
-  }
-  c->stack_entries = std::max(2, depth + 1);
-  c->wide = wide;
-  c->qroot = qroot;
-  c->qstack_entries = std::max(2, 3 * qdepth + 2);
-  c->tri_mat.assign(s->material_id, s->material_id + nt);
-  c->mat_table = mt;
+  if ((rc = upload(c, (void**)&c->d_qnodes, k.qnodes.data(), k.qnodes.size() * sizeof(scn::WNode)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_nodes, k.nodes.data(), k.nodes.size() * sizeof(scn::BNode)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_tri, k.tri.data(), k.tri.size() * sizeof(float)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_trx, k.trx.data(), k.trx.size() * sizeof(float)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_trin, k.trin.data(), k.trin.size() * sizeof(float)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_hrec, k.hrec.data(), k.hrec.size() * sizeof(float)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_mats, k.mats.data(), k.mats.size() * sizeof(float)))) return rc;
+  c->n_qnodes = (int)k.qnodes.size();
+  c->tri_k1 = k.tri_k1; c->tri_k0 = k.tri_k0; c->tri_flagged = k.tri_flagged;
+  c->n_tri = k.n_tri;
+  c->n_mats = k.n_mats;
+  c->root = k.root;
+  c->has_scene = k.has_scene;
+  c->cull_R = k.cull_R; c->cull_K = k.cull_K; c->cull_off = k.cull_off;
+  c->stack_entries = std::max(2, k.depth + 1);
+  c->wide = k.wide;
+  c->qroot = k.qroot;
+  c->qstack_entries = std::max(2, 3 * k.qdepth + 2);
+  c->tri_mat = std::move(k.tri_mat);
+  c->mat_table = std::move(k.mats);
   c->scene_set = true;
   return occupancy(c);
 }
 
 int rt_set_scene_encoded(rt_ctx* c, const float* tri_enc, int32_t n_triangles, const float* node_enc, int32_t n_nodes) {
   if (!c || n_triangles < 0 || n_nodes < 0 || (n_triangles && !tri_enc) || (n_nodes && !node_enc)) return RT_ERR_ARG;
-  const size_t nt = (size_t)n_triangles;
-  std::vector<float> p[6];
-  for (auto& v : p) v.resize(3 * nt);
-  std::vector<int32_t> mid(nt);
-  std::vector<rt_material> mats;
-  for (size_t i = 0; i < nt; i++) {
-    const float* t = tri_enc + 42 * i;  // Triangle_encoded: 14 texels
-    for (int k = 0; k < 6; k++) memcpy(&p[k][3 * i], t + 3 * k, 12);
-    rt_material m;
-    memcpy(&m, t + 18, sizeof(rt_material));
-    int found = -1;
-    for (size_t q = 0; q < mats.size(); q++)
-      if (!memcmp(&mats[q], &m, sizeof(m))) { found = (int)q; break; }
-    if (found < 0) { mats.push_back(m); found = (int)mats.size() - 1; }
-    mid[i] = found;
-  }
-  std::vector<int32_t> L(n_nodes), R(n_nodes), N(n_nodes), I(n_nodes);
-  std::vector<float> aa(3 * (size_t)n_nodes), bb(3 * (size_t)n_nodes);
-  for (int i = 0; i < n_nodes; i++) {  // BVHNode_encoded: ints stored as floats (RT:224-230 casts)
-    const float* nd = node_enc + 12 * (size_t)i;
-    L[i] = (int)nd[0]; R[i] = (int)nd[1]; N[i] = (int)nd[3]; I[i] = (int)nd[4];
-    memcpy(&aa[3 * i], nd + 6, 12);
-    memcpy(&bb[3 * i], nd + 9, 12);
-  }
-  rt_scene_soa s;
-  s.n_triangles = n_triangles;
-  s.p1 = p[0].data(); s.p2 = p[1].data(); s.p3 = p[2].data();
-  s.n1 = p[3].data(); s.n2 = p[4].data(); s.n3 = p[5].data();
-  s.material_id = mid.data();
-  s.materials = mats.data();
-  s.n_materials = (int32_t)mats.size();
-  s.n_nodes = n_nodes;
-  s.node_left = L.data(); s.node_right = R.data(); s.node_n = N.data(); s.node_index = I.data();
-  s.node_aa = aa.data(); s.node_bb = bb.data();
-  return rt_set_scene(c, &s);
+  scn::Decoded d;
+  scn::decode(tri_enc, n_triangles, node_enc, n_nodes, d);
+  return rt_set_scene(c, &d.soa);
 }
 
 int rt_update_materials(rt_ctx* c, int32_t first, int32_t count, const rt_material* m) {
@@ -1204,7 +730,7 @@ int rt_update_materials(rt_ctx* c, int32_t first, int32_t count, const rt_materi
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = drain(c)) return rc;
   float packed[32];
-  pack_material(*m, packed);
+  scn::pack_material(*m, packed);
   int id = -1;
   for (int k = 0; k < c->n_mats; k++)
     if (!memcmp(&c->mat_table[32 * k], packed, sizeof(packed))) { id = k; break; }

@@ -7,6 +7,7 @@
 // reproduces the reference's BVH node arrays bit for bit.  Compiled with
 // -ffp-contract=off (no FMA contraction, as the reference's x86-64 SSE build).
 #include "rt_scene.h"
+#include "scene_compile.h"
 #include "tri_filter.h"
 
 #include <math.h>
@@ -1301,3 +1302,46 @@ int rts_tri_filter(const float* tri, int n_triangles, float* out, double* k, int
   if (flagged) *flagged = c.flagged;
   return 0;
 }
+
+// ---- the HIP path's scene compiler (csrc/common/scene_compile.h), for tests and tooling
+struct rts_compiled {
+  scn::Compiled c;
+  std::string err;
+};
+
+static scn::Options compile_options(const int32_t* o) {
+  scn::Options opt;
+  if (o) { opt.rebuild = o[0] != 0; opt.greedy = o[1] != 0; opt.bfs = o[2] != 0; opt.wide = o[3] != 0; }
+  return opt;
+}
+
+int rts_compile_scene(const struct rt_scene_soa* scene, const int32_t* options, rts_compiled** out) {
+  if (!scene || !out) return RTS_ERR_ARG;
+  *out = new (std::nothrow) rts_compiled();
+  if (!*out) return RTS_ERR_NOMEM;
+  return scn::compile(scene, compile_options(options), (*out)->c, (*out)->err);
+}
+
+int rts_compile_scene_encoded(const float* tri_enc, int32_t n_triangles, const float* node_enc, int32_t n_nodes,
+                              const int32_t* options, rts_compiled** out) {
+  if (!out || n_triangles < 0 || n_nodes < 0 || (n_triangles && !tri_enc) || (n_nodes && !node_enc)) return RTS_ERR_ARG;
+  scn::Decoded d;
+  scn::decode(tri_enc, n_triangles, node_enc, n_nodes, d);
+  return rts_compile_scene(&d.soa, options, out);
+}
+
+int rts_compiled_get(const rts_compiled* k, rts_compiled_view* v) {
+  if (!k || !v) return RTS_ERR_ARG;
+  const scn::Compiled& c = k->c;
+  *v = rts_compiled_view{c.tri.data(), c.trx.data(), c.trin.data(), c.hrec.data(), c.mats.data(),
+                         c.nodes.data(), c.qnodes.data(), c.tri_mat.data(),
+                         (int64_t)c.tri.size(), (int64_t)c.trx.size(), (int64_t)c.trin.size(), (int64_t)c.hrec.size(),
+                         (int64_t)c.mats.size(), (int64_t)c.nodes.size(), (int64_t)c.qnodes.size(),
+                         (int64_t)c.tri_mat.size(),
+                         c.cull_R, c.cull_K, c.cull_off, c.tri_k1, c.tri_k0,
+                         c.n_tri, c.n_mats, c.root, c.has_scene, c.depth, c.qroot, c.qdepth, c.wide ? 1 : 0,
+                         c.tri_flagged, k->err.c_str()};
+  return RTS_OK;
+}
+
+void rts_compiled_free(rts_compiled* k) { delete k; }

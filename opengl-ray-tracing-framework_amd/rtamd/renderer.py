@@ -85,6 +85,34 @@ class RtSceneSoa(C.Structure):
     ]
 
 
+def marshal_scene_soa(soa: dict, nodes: dict):
+    """rt_scene_soa over soa (rts_scene_export_soa() arrays) and nodes (rts_scene_nodes() arrays,
+    reference numbering), for rt_set_scene and rts_compile_scene.  An entry that is None becomes a
+    null pointer.  Returns the struct and the arrays it points into (keep them alive with it)."""
+    def arr(d, k, dtype):
+        return None if d.get(k) is None else np.ascontiguousarray(d[k], dtype)
+    keep = {k: arr(soa, k, np.float32) for k in ("p1", "p2", "p3", "n1", "n2", "n3")}
+    mid = arr(soa, "material_id", np.int32)
+    mats_np = np.ascontiguousarray(soa["materials"], np.float32).reshape(-1, 24)
+    mats = (RtMaterial * max(1, len(mats_np)))()
+    for i, row in enumerate(mats_np):
+        for k in range(24):
+            mats[i].v[k] = float(row[k])
+    nd = {k: arr(nodes, k, np.int32) for k in ("left", "right", "n", "index")}
+    aa, bb = arr(nodes, "aa", np.float32), arr(nodes, "bb", np.float32)
+    s = RtSceneSoa()
+    s.n_triangles = len(keep["p1"]) if mid is None else len(mid)
+    s.p1, s.p2, s.p3 = _fp(keep["p1"]), _fp(keep["p2"]), _fp(keep["p3"])
+    s.n1, s.n2, s.n3 = _fp(keep["n1"]), _fp(keep["n2"]), _fp(keep["n3"])
+    s.material_id = _ip(mid)
+    s.materials = mats
+    s.n_materials = len(mats_np)
+    s.n_nodes = max((len(a) for a in nd.values() if a is not None), default=0)
+    s.node_left, s.node_right, s.node_n, s.node_index = (_ip(nd[k]) for k in ("left", "right", "n", "index"))
+    s.node_aa, s.node_bb = _fp(aa), _fp(bb)
+    return s, (keep, mid, mats, nd, aa, bb)
+
+
 class RtTiling(C.Structure):
     _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("rank", C.c_int32), ("world", C.c_int32)]
 
@@ -246,11 +274,11 @@ def _bind(L: C.CDLL) -> C.CDLL:
 
 
 def _fp(a):
-    return a.ctypes.data_as(_f32p)
+    return None if a is None else a.ctypes.data_as(_f32p)
 
 
 def _ip(a):
-    return a.ctypes.data_as(_i32p)
+    return None if a is None else a.ctypes.data_as(_i32p)
 
 
 class Renderer:
@@ -292,26 +320,7 @@ class Renderer:
     # ------------------------------------------------------------ static data
     def set_scene_soa(self, soa: dict, nodes: dict) -> None:
         """soa: rts_scene_export_soa() arrays; nodes: rts_scene_nodes() arrays (reference numbering)."""
-        keep = {k: np.ascontiguousarray(soa[k], np.float32) for k in ("p1", "p2", "p3", "n1", "n2", "n3")}
-        mid = np.ascontiguousarray(soa["material_id"], np.int32)
-        mats_np = np.ascontiguousarray(soa["materials"], np.float32).reshape(-1, 24)
-        mats = (RtMaterial * max(1, len(mats_np)))()
-        for i, row in enumerate(mats_np):
-            for k in range(24):
-                mats[i].v[k] = float(row[k])
-        nd = {k: np.ascontiguousarray(nodes[k], np.int32) for k in ("left", "right", "n", "index")}
-        aa = np.ascontiguousarray(nodes["aa"], np.float32)
-        bb = np.ascontiguousarray(nodes["bb"], np.float32)
-        s = RtSceneSoa()
-        s.n_triangles = len(mid)
-        s.p1, s.p2, s.p3 = _fp(keep["p1"]), _fp(keep["p2"]), _fp(keep["p3"])
-        s.n1, s.n2, s.n3 = _fp(keep["n1"]), _fp(keep["n2"]), _fp(keep["n3"])
-        s.material_id = _ip(mid)
-        s.materials = mats
-        s.n_materials = len(mats_np)
-        s.n_nodes = len(nd["left"])
-        s.node_left, s.node_right, s.node_n, s.node_index = (_ip(nd[k]) for k in ("left", "right", "n", "index"))
-        s.node_aa, s.node_bb = _fp(aa), _fp(bb)
+        s, _keep = marshal_scene_soa(soa, nodes)
         self._check(self._L.rt_set_scene(self._h, C.byref(s)), "rt_set_scene")
 
     def set_scene_encoded(self, tri_enc: np.ndarray, node_enc: np.ndarray) -> None:

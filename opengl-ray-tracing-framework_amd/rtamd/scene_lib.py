@@ -81,6 +81,25 @@ class Material:
         return cls(tuple(t[0:3]), tuple(t[3:6]), *t[6:18], tuple(t[18:21]), *t[21:24])
 
 
+class RtsCompiledView(C.Structure):
+    _fields_ = ([(k, _f32p) for k in ("tri", "trx", "trin", "hrec", "mats")]
+                + [("nodes", C.c_void_p), ("qnodes", C.c_void_p), ("tri_mat", _i32p)]
+                + [(k, C.c_int64) for k in ("n_tri_f", "n_trx_f", "n_trin_f", "n_hrec_f", "n_mats_f", "n_nodes",
+                                            "n_qnodes", "n_tri_mat")]
+                + [(k, C.c_double) for k in ("cull_R", "cull_K", "cull_off", "tri_k1", "tri_k0")]
+                + [(k, C.c_int32) for k in ("n_tri", "n_mats", "root", "has_scene", "depth", "qroot", "qdepth",
+                                            "wide", "tri_flagged")]
+                + [("err", C.c_char_p)])
+
+
+# the scene compiler's records (csrc/common/scene_compile.h scn::BNode, scn::WNode)
+BNODE_DTYPE = np.dtype([("box", np.float32, 12), ("ref", np.int32, 4)])
+WNODE_DTYPE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("ref", np.int32, 4),
+                        ("pad", np.int32, 4)])
+Q_EMPTY = 0x7fffffff
+LEAF_BIT = 0x80000000
+
+
 _lib = None
 
 
@@ -120,6 +139,11 @@ def lib() -> C.CDLL:
         L.rts_glibc_rand.argtypes = [C.c_uint, C.c_int, C.POINTER(C.c_int)]
         L.rts_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
         L.rts_tri_filter.argtypes = [_f32p, C.c_int, _f32p, C.POINTER(C.c_double), _i32p]
+        L.rts_compile_scene.argtypes = [vp, _i32p, C.POINTER(vp)]
+        L.rts_compile_scene_encoded.argtypes = [_f32p, C.c_int32, _f32p, C.c_int32, _i32p, C.POINTER(vp)]
+        L.rts_compiled_get.argtypes = [vp, C.POINTER(RtsCompiledView)]
+        L.rts_compiled_free.argtypes = [vp]
+        L.rts_compiled_free.restype = None
         _lib = L
     return _lib
 
@@ -332,6 +356,68 @@ def tri_filter(tri: np.ndarray):
     fl = np.zeros(1, np.int32)
     _check(lib().rts_tri_filter(_fp(tri), n, _fp(out), k, _ip(fl)), "rts_tri_filter")
     return out, float(k[0]), float(k[1]), int(fl[0])
+
+
+@dataclasses.dataclass
+class CompiledScene:
+    """What rt_set_scene uploads and commits for a scene (scn::Compiled), or why it refuses it."""
+    rc: int                 # rt_set_scene's code: 0, RT_ERR_ARG (-1) or RT_ERR_LIMIT (-6)
+    err: str
+    arrays: dict            # tri, trx, trin, hrec (n, 4) float32; mats (n, 32); nodes, qnodes; tri_mat
+    scalars: dict
+
+
+def _compiled(rc: int, h) -> CompiledScene:
+    L = lib()
+    try:
+        v = RtsCompiledView()
+        _check(L.rts_compiled_get(h, C.byref(v)), "rts_compiled_get")
+
+        def take(ptr, n, dtype, ctype):
+            if n == 0:
+                return np.zeros(0, dtype)
+            buf = C.cast(ptr, C.POINTER(ctype * (n * np.dtype(dtype).itemsize // C.sizeof(ctype)))).contents
+            return np.frombuffer(buf, dtype=dtype, count=n).copy()
+        a = {k: take(getattr(v, k), getattr(v, f"n_{k}_f"), np.float32, C.c_float).reshape(-1, 32 if k == "mats" else 4)
+             for k in ("tri", "trx", "trin", "hrec", "mats")}
+        a["nodes"] = take(v.nodes, v.n_nodes, BNODE_DTYPE, C.c_float)
+        a["qnodes"] = take(v.qnodes, v.n_qnodes, WNODE_DTYPE, C.c_float)
+        a["tri_mat"] = take(v.tri_mat, v.n_tri_mat, np.int32, C.c_int32)
+        sc = {k: getattr(v, k) for k in ("cull_R", "cull_K", "cull_off", "tri_k1", "tri_k0", "n_tri", "n_mats", "root",
+                                         "has_scene", "depth", "qroot", "qdepth", "tri_flagged")}
+        sc["wide"] = bool(v.wide)
+        return CompiledScene(rc, (v.err or b"").decode(), a, sc)
+    finally:
+        L.rts_compiled_free(h)
+
+
+def _options(rebuild, greedy, bfs, wide):
+    return np.array([rebuild, greedy, bfs, wide], np.int32)
+
+
+def compile_scene(soa, nodes: Optional[dict] = None, *, rebuild=True, greedy=False, bfs=True, wide=True) -> CompiledScene:
+    """The HIP path's scene compiler (csrc/common/scene_compile.h, the code rt_set_scene runs) on
+    soa / nodes as Renderer.set_scene_soa takes them, or on a ready RtSceneSoa."""
+    from .renderer import marshal_scene_soa
+    s, _keep = (soa, None) if nodes is None else marshal_scene_soa(soa, nodes)
+    h = C.c_void_p()
+    rc = lib().rts_compile_scene(C.byref(s), _ip(_options(rebuild, greedy, bfs, wide)), C.byref(h))
+    if not h.value:
+        raise RuntimeError(f"rts_compile_scene failed with {rc}")
+    return _compiled(rc, h)
+
+
+def compile_scene_encoded(tri_enc: np.ndarray, node_enc: np.ndarray, *, rebuild=True, greedy=False, bfs=True,
+                          wide=True) -> CompiledScene:
+    """The same from the reference's encodings, as Renderer.set_scene_encoded takes them."""
+    t = np.ascontiguousarray(tri_enc, np.float32)
+    n = np.ascontiguousarray(node_enc, np.float32)
+    h = C.c_void_p()
+    rc = lib().rts_compile_scene_encoded(_fp(t), t.shape[0], _fp(n), n.shape[0],
+                                         _ip(_options(rebuild, greedy, bfs, wide)), C.byref(h))
+    if not h.value:
+        raise RuntimeError(f"rts_compile_scene_encoded failed with {rc}")
+    return _compiled(rc, h)
 
 
 def write_png(path: str, rgb: np.ndarray) -> None:

@@ -2,7 +2,7 @@
 triangle test, evaluated in fp32 exactly as RT:241-299 does.
 
 The GPU skips a subtree when its box entry t0 exceeds cull_limit(best) = best + 1e-3 +
-1e-3*best + eps*max|1/d_a| (rt_kernels.h), with eps from cull_bound_stats (rt_render.hip):
+1e-3*best + eps*max|1/d_a| (rt_kernels.h), with eps from cull_bound_stats (scene_compile.h):
 eps = 2 (K u R + off), K = max over triangles of 44 + 70/cos(theta), u = 2^-24.  That is exact
 (never drops the reference's closest hit) if every hit the reference accepts has its point
 X = S + d*t within eps/2 of the triangle (so of every box holding it).  Here millions of
@@ -33,7 +33,7 @@ def cross(a, b):
 
 
 def geometric_normal(p1, p2, p3):
-    """rt_render.hip geometric_normal: the fp32 operations of normalize(cross(p2-p1, p3-p1))."""
+    """scene_compile.h geometric_normal: the fp32 operations of normalize(cross(p2-p1, p3-p1))."""
     c = cross(p2 - p1, p3 - p1)
     with np.errstate(all="ignore"):
         inv = F(1) / np.sqrt(dot(c, c))
@@ -59,8 +59,8 @@ def hit_triangle(p1, p2, p3, N, S, d):
 
 def per_triangle_bound(p1, p2, p3, N, R):
     """cull_bound_stats per triangle: K u R + off (in float64), K = inf when badly conditioned."""
-    a = (p2 - p1).astype(np.float64)
-    b = (p3 - p1).astype(np.float64)
+    a = p2.astype(np.float64) - p1.astype(np.float64)   # the edges in float64, as cull_bound_stats takes them
+    b = p3.astype(np.float64) - p1.astype(np.float64)
     cx = np.cross(a, b)
     nrm = np.linalg.norm(cx, axis=-1)
     with np.errstate(all="ignore"):

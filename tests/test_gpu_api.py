@@ -114,6 +114,27 @@ def test_empty_scene_renders_the_environment(gpu_renderer, env_maps):
         assert bit_mismatch(img, ref)[0] == 0.0
 
 
+def test_rejected_scene_changes_nothing(gpu_renderer, env_maps):
+    """rt_set_scene compiles the scene before it touches the device or the context: a scene it
+    refuses (here: a leaf of 17 triangles) leaves the previous one rendering as before."""
+    sd = cf.config_scene("C2")
+    W, H = 16, 9
+    fp = cf.frame_params(W, H)
+    ro = cf.rand_origins(1)
+    r = gpu_renderer
+    img, st = gpu_render(r, sd, env_maps, W, H, fp, ro)
+    bad = {k: v.copy() for k, v in sd.nodes.items()}
+    bad["n"][int(np.flatnonzero(bad["n"][1:] > 0)[0]) + 1] = 17
+    with pytest.raises(RuntimeError, match=r"rt_set_scene failed \(-6\): leaf with more than 16 triangles"):
+        r.set_scene_soa(sd.soa, bad)
+    r.clear_accum()
+    r.set_loop_num(0)
+    r.reset_stats()
+    st2 = r.render(fp, ro)
+    assert bit_mismatch(r.read_accum(), img)[0] == 0.0
+    assert st2["rays"] == st["rays"] > 0
+
+
 @pytest.mark.parametrize("assign", ["modulo", "balanced"])
 @pytest.mark.parametrize("world", [2, 3])
 def test_tile_split_and_device_assembly(gpu_renderer, env_maps, world, assign):

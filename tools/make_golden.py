@@ -8,6 +8,8 @@
 * bvh_counts.json     node / leaf / depth counts measured from the reference BVH.h (SURVEY.md
                       §8(c) table) — copied, not recomputed
 * scene_hashes.json   sha256 of our encoded C2/C3 arrays (regression of the host pipeline)
+* compiled_scene_hashes.json  sha256 of the arrays the scene compiler (csrc/common/scene_compile.h)
+                      makes of C2/C3 at the default options: what rt_set_scene uploads
 * oracle_*.npy        small oracle renders (regression of the oracle itself)
 """
 import hashlib
@@ -79,6 +81,14 @@ def main() -> int:
         hashes[name] = {"tri_enc": hashlib.sha256(sd.tri_enc.tobytes()).hexdigest(),
                         "node_enc": hashlib.sha256(sd.node_enc.tobytes()).hexdigest()}
     (GOLD / "scene_hashes.json").write_text(json.dumps(hashes, indent=1))
+
+    compiled = {}
+    for name in ("C2", "C3"):
+        sd = cf.config_scene(name)
+        k = sl.compile_scene(sd.soa, sd.nodes)
+        compiled[name] = {a: hashlib.sha256(k.arrays[a].tobytes()).hexdigest()
+                          for a in ("tri", "trx", "trin", "hrec", "mats", "nodes", "qnodes")}
+    (GOLD / "compiled_scene_hashes.json").write_text(json.dumps(compiled, indent=1))
 
     import oracle as orc
     env = cf.load_env()
