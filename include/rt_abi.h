@@ -131,7 +131,11 @@ enum {
 };
 
 typedef struct rt_stats {
-  uint64_t rays;            /* hitBVH invocations: camera + NEE shadow + continuation    */
+  uint64_t rays;            /* hitBVH invocations of the reference: camera + NEE shadow +
+                               continuation, one camera ray per sample.  A group of several
+                               frames answers a pixel's camera rays with one traversal (the
+                               same ray in every frame), so rays / time is not a traversal
+                               rate for the camera pass: compare builds on time per frame   */
   uint64_t samples;         /* pixel samples traced (frames x pixels, R12 copies excluded) */
   uint64_t internal_pops, leaf_pops, tri_tests;  /* only with RT_FLAG_COUNT_VISITS */
   uint64_t launches;        /* rt_render_async calls that launched work                  */

@@ -85,8 +85,9 @@ int dev_pass_report(rt_ctx* c, hipStream_t st, const rtd::WFParams& WP, int g, i
   HIPCHK(c, hipMemcpy(h, c->d_stats, sizeof(h), hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(q, WP.S.cnt, sizeof(q), hipMemcpyDeviceToHost));
   q[0] = q[rtd::cq(pass & 1)] + (WP.split ? q[rtd::cqs(pass & 1)] : 0u);  // (split queues: both kinds)
+  const unsigned int traced = WP.cam_n ? (WP.cam_shared ? WP.K.n_work : WP.cam_n) : q[0];  // traversals of the launch
   fprintf(stderr, "[rt] group %d pass %d: %u rays %.3f ms  cum internal %llu leaf %llu tri %llu iters %llu "
-          "wave-iters max %llu ray-steps max %llu\n", g, pass, (WP.cam_n ? WP.cam_n : q[0]), ms, h[2], h[3], h[4], h[5], h[6], h[7]);
+          "wave-iters max %llu ray-steps max %llu\n", g, pass, traced, ms, h[2], h[3], h[4], h[5], h[6], h[7]);
   unsigned long long hq[6];
   HIPCHK(c, hipMemcpy(hq, c->d_stats + 22, sizeof(hq), hipMemcpyDeviceToHost));
   fprintf(stderr, "[rt]   4-wide node visits with BFS index < 1 / 5 / 21 / 64 / 85 / 341: %llu %llu %llu %llu %llu %llu\n",
@@ -96,7 +97,7 @@ int dev_pass_report(rt_ctx* c, hipStream_t st, const rtd::WFParams& WP, int g, i
           "refill %.3f (%llu outer)\n", h[9] / (64.0 * (double)(h[8] + !h[8])), h[8],
           h[11] / (64.0 * (double)(h[10] + !h[10])), h[10], h[13] / (64.0 * (double)(h[12] + !h[12])), h[12]);
   fprintf(stderr, "[rt]   overflow-column pushes %llu (%.3f per ray)\n", h[14],
-          (double)h[14] / (double)std::max(1u, WP.cam_n ? WP.cam_n : q[0]));
+          (double)h[14] / (double)std::max(1u, traced));
   HIPCHK(c, hipMemset(c->d_stats + 6, 0, 10 * sizeof(unsigned long long)));
   {  // steps-per-ray histogram (16-step buckets) by ray kind
     unsigned long long hh[64];

@@ -128,6 +128,16 @@ struct rt_ctx {
 #ifndef RT_CAM_SHADE  // the bulk camera pass's shade in its own instantiation (wf_shade<..., CAM>)
 #define RT_CAM_SHADE 1
 #endif
+#ifndef RT_CAM_SHARED  // groups of several frames trace each pixel's camera ray once (WFParams::cam_shared)
+#define RT_CAM_SHARED 1
+#endif
+#ifndef RT_CAM_SHARED_STATIC  // a bulk group's shared camera trace (one ray per work item: a small pass) runs the
+                              // bulk's instantiation (0) or the small passes' (1: static shares, lane quads, every
+                              // claim 64 rays): C3, 2.07 M rays of one 256-frame group standalone 0.299 vs 0.662 ms
+                              // (11 ms per slot before), whole step +0.2% (noise); profiles/r07_passes256_*_C3.log,
+                              // profiles/r07_ab_proc_shared_camera_C3.log
+#define RT_CAM_SHARED_STATIC 0
+#endif
 #ifndef RT_POOL_CHUNK_DEFAULT
 #define RT_POOL_CHUNK_DEFAULT 1024
 #endif
@@ -411,7 +421,8 @@ void launch_trace_t(rt_ctx* c, dim3 grid, const rtd::WFParams& WP, hipStream_t s
   else launch_trace_w<COUNT, false>(c, grid, WP, st, small);
 }
 
-// small: a frame group of at most finish_slots path slots (one frame per call)
+// small: a frame group of at most finish_slots path slots (one frame per call), or a bulk
+// group's shared camera trace (one ray per work item)
 void launch_trace(rt_ctx* c, bool count, dim3 grid, const rtd::WFParams& WP, hipStream_t st, bool small) {
   if (count) launch_trace_t<true>(c, grid, WP, st, small);
   else launch_trace_t<false>(c, grid, WP, st, small);
@@ -1282,6 +1293,7 @@ int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, co
     WP.n_frames = f1 - f0;
     WP.pass = 0;
     WP.cam_n = 0u;
+    WP.cam_shared = 0;
     // (not for frame groups of one frame each: their blends must run in frame order)
     WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
     plan.slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
@@ -1355,12 +1367,22 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
     }
     // pass 0's camera paths are implicit (wf_trace / wf_shade generate them)
     WP.cam_n = pass == 0 ? slots : 0u;
+    // a group of several frames traces each work item's camera ray once and every frame's shade
+    // reads that result.  The counting runs (RT_FLAG_COUNT_VISITS, and with it the rt_tile_costs /
+    // rt_order_work probes and the counting per-pass reports) keep one traversal per path slot:
+    // their counters are the steps of the rays counted in rt_stats.rays, and the tile balance is
+    // calibrated on them.
+    bool cam_shared = RT_CAM_SHARED && pass == 0 && WP.n_frames > 1 && !count && !c->tile_cost_on;
+    bool cam_static = RT_CAM_SHARED_STATIC != 0;
+    if (const char* e = knob("RT_CAM_SHARED")) cam_shared = cam_shared && atoi(e) != 0;  // (A/B)
+    if (const char* e = knob("RT_CAM_SHARED_STATIC")) cam_static = atoi(e) != 0;           // (A/B)
+    WP.cam_shared = cam_shared ? 1 : 0;
     hipEvent_t t0, t1;
     TAKE_EVENT(c, t0);
     TAKE_EVENT(c, t1);
     HIPCHK(c, hipEventRecord(t0, st));
     launch_trace(c, count, dim3((unsigned)(c->n_cus * (pass == 0 ? c->trace_bpc0 : c->trace_bpc))), WP, st,
-                 slots <= c->finish_slots);
+                 slots <= c->finish_slots || (cam_shared && cam_static));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, st));
     c->trace_events.push_back({t0, t1, c->launches});

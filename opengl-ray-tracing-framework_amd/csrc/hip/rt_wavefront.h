@@ -143,6 +143,13 @@ struct WFParams {
   // paths of slots [0, cam_n) in slot order (entry i = slot i), generated where they are used
   // (wf_trace refill, wf_shade) instead of being written by a generation kernel and read back
   unsigned int cam_n;
+  // pass 0 of a group of several frames: the camera trace has one queue entry per work item
+  // (entry i = work item i, ray S.cam[i] from P.pos) and writes the pixel's result to frame 0's
+  // slot, S.res[2 * (i * n_frames)]; every frame's shade reads that slot (cam_slot).  A pixel's
+  // frames trace the same camera ray (R6: no jitter), and the traversal is a function of the ray.
+  // Off for the counting runs, whose counters are per ray of rt_stats.rays; cam_n stays `slots`
+  // (the shade's paths, and the camera rays counted in rt_stats.rays: one per sample)
+  int cam_shared;
   int p1_compact;  // pass 0 queues 16-B rays from the per-pixel origin (off when the finisher starts at pass 1)
   // one frame per path-state set and nothing in flight before it (unpipelined calls of one frame
   // per group): a finishing path blends into the accumulation itself (wf_blend's operations,
@@ -270,9 +277,13 @@ RTD void sobol_pair(const KParams& P, uint32_t frame, uint32_t bounce, float& sx
 }
 
 // Camera ray of path slot `slot`: direction, seed (R5) and frame of the slot.  Path slots are
-// pixel-major (slot = work item * n_frames + frame): the camera pass hands a wave one pixel's
-// frames, whose camera rays are the same ray (R6: no jitter), so its lanes traverse in lockstep,
-// and the next passes start from the same hit point.
+// pixel-major (slot = work item * n_frames + frame).  A pixel's frames have the same camera ray
+// (R6: no jitter) and differ in the seed alone, which the traversal does not read: a group of
+// several frames traces it once per pixel (WFParams::cam_shared), and the next passes of all its
+// frames start from that one hit point.
+// the slot that holds the camera trace's result for path slot `slot` of frame `frame`: its own,
+// or with WFParams::cam_shared its pixel's frame 0
+RTD unsigned int cam_slot(const WFParams& W, unsigned int slot, uint32_t frame) { return W.cam_shared ? slot - frame : slot; }
 RTD f3 camera_ray(const KParams& P, const WFState& S, unsigned int slot, uint32_t& wseed, uint32_t& frame) {
   const unsigned int nf = (unsigned int)P.n_frames;
   const unsigned int w = slot / nf;
@@ -1094,7 +1105,9 @@ RTD int coop_move(TraceLane& L, const TraceStack& TS, unsigned long long live, i
 #define RT_TRACE_WPE_DUAL 8
 #endif
 // CAM: the implicit camera pass (WFParams::cam_n); a separate instantiation so the secondary
-// passes' kernels carry none of its registers.  STATIC: small groups' static first shares (below;
+// passes' kernels carry none of its registers.  Its queue is one entry per path slot, or with
+// WFParams::cam_shared one per work item (the pixel's one camera ray, result to frame 0's slot).
+// STATIC: small groups' static first shares (below;
 // a separate instantiation: the code alone cost the bulk's kernels 0.4%).
 // KIND: 0 the pass's one queue (both kinds); with split queues (WFParams::split) 1 the
 // continuations (closest hit) and 2 the shadow rays (any hit: no culling, no child sort, AH
@@ -1107,7 +1120,9 @@ void wf_trace(const WFParams W) {
   const WFState& S = W.S;
   const int qin = W.pass & 1;
   constexpr bool AHK = KIND == 2;  // every ray of the launch is any-hit
-  const unsigned int nq = CAM ? W.cam_n : AHK ? S.cnt[cqs(qin)] : S.cnt[cq(qin)];
+  const bool shared = CAM && W.cam_shared;  // one camera ray per work item: entry i = slot i * n_frames
+  const unsigned int cam_stride = shared ? (unsigned int)W.n_frames : 1u;
+  const unsigned int nq = CAM ? (shared ? P.n_work : W.cam_n) : AHK ? S.cnt[cqs(qin)] : S.cnt[cq(qin)];
   const int* __restrict__ Q = AHK ? S.queue_s[qin] : S.queue[qin];
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // the shade pass after us appends here
     S.cnt[cq(qin ^ 1)] = 0u;
@@ -1117,7 +1132,7 @@ void wf_trace(const WFParams W) {
   if (nq == 0u || !P.has_scene) {
     if (!P.has_scene) {  // empty scene: every ray misses (RT:346 reads a zero node)
       for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
-        const int e = CAM ? (int)(i << 1) : Q[i];
+        const int e = CAM ? (int)((i * cam_stride) << 1) : Q[i];
         S.res[e] = -1;
       }
     }
@@ -1233,12 +1248,11 @@ void wf_trace(const WFParams W) {
         const unsigned int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
         if (!busy && rank < avail) {
           const unsigned int qi = pool_next + rank;
-          if (CAM) {  // implicit camera pass: queue entry i is slot i's camera ray
-            const unsigned int slot = qi;
+          if (CAM) {  // implicit camera pass: queue entry i is slot i's camera ray, or work item i's
+            const unsigned int slot = qi * cam_stride;
             entry = (int)(slot << 1);
             L.anyhit = false;
-            uint32_t seed_unused, frame_unused;
-            const f3 d = camera_ray(P, S, slot, seed_unused, frame_unused);
+            const float4 d = S.cam[shared ? qi : slot / (unsigned int)P.n_frames];
             L.ox = P.pos[0]; L.oy = P.pos[1]; L.oz = P.pos[2];
             L.dx = d.x; L.dy = d.y; L.dz = d.z;
           } else {
@@ -1468,9 +1482,10 @@ RTD HitGeom hit_geom(const KParams& P, int tri, f3 ro, f3 rd) {
 // or the environment colour of a miss -- is computed once per pixel into LDS (kCamRec float4) by
 // cam_rec and read by the frames' lanes (same functions on the same values: the same bits), with
 // the terms of the BSDF calls that depend on V and the material alone (v_terms: DisneySample's
-// lobe weights, the VNDF frame, the V-side Fresnel and masking terms).  Every frame of a pixel has
-// the record's trace result (the same ray, and a closest hit that is a function of the ray:
-// RT_CHECK reports any frame that does not).  The other instantiations carry none of it (a
+// lobe weights, the VNDF frame, the V-side Fresnel and masking terms).  The record is built from
+// the pixel's one camera trace result (WFParams::cam_shared: frame 0's slot; without it every
+// frame traces the same ray to the same closest hit, and the record still reads frame 0's).
+// The other instantiations carry none of it (a
 // runtime record path in them cost the later passes' shades 2 ms per 256-frame group).
 constexpr int kCamRec = 11;  // [0..6] the hit, [7..10] v_terms
 RTD void cam_rec(const WFParams& W, const Env& E, unsigned int w, float4* rec) {
@@ -1559,7 +1574,9 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
         a3 = S.s3[path];
       }
     }
-    const int rc0 = S.res[2 * path];
+    // (pass 0 with cam_shared: the pixel's one camera result, in frame 0's slot; the pass-0 results
+    // of the other frames' slots are never written)
+    const int rc0 = S.res[2 * (camPass ? (int)cam_slot(W, (unsigned)path, a5.w) : path)];
 #ifdef RT_CHECK
     if (CAMK && __float_as_int(rec[1].w) != rc0)
       printf("[rt check] camera record: path %d result %d, record %d\n", path, rc0, __float_as_int(rec[1].w));
@@ -1600,8 +1617,8 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
       doFinish = true;
     } else {
       // the CAM pass branches on the record's own result (rec[1].w, written on hit and miss alike),
-      // so both record branches read initialised LDS; a frame whose own result differed would be
-      // reported by the RT_CHECK build above (none is: every frame traces the same camera ray, R6)
+      // so both record branches read initialised LDS; rc0 is the same slot's value (the RT_CHECK
+      // build above compares them: the record and the other shades' pass-0 read agree)
       const int r = useRec ? __float_as_int(rec[1].w) : rc0;
       const float4 oo = oo0, dd = dd0;
       const f3 ro = xyz(oo), rd = xyz(dd);
