@@ -131,6 +131,10 @@ struct rt_ctx {
 #ifndef RT_CAM_SHARED  // groups of several frames trace each pixel's camera ray once (WFParams::cam_shared)
 #define RT_CAM_SHARED 1
 #endif
+#ifndef RT_CAM_MISS_ONCE  // bulk groups that run the shared camera trace and wf_shade<..., CAM> handle a pixel whose
+                          // camera ray misses once per group, not once per frame (WFParams::cam_miss_once)
+#define RT_CAM_MISS_ONCE 1
+#endif
 #ifndef RT_CAM_SHARED_STATIC  // a bulk group's shared camera trace (one ray per work item: a small pass) runs the
                               // bulk's instantiation (0) or the small passes' (1: static shares, lane quads, every
                               // claim 64 rays): C3, 2.07 M rays of one 256-frame group standalone 0.299 vs 0.662 ms
@@ -1294,6 +1298,7 @@ int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, co
     WP.pass = 0;
     WP.cam_n = 0u;
     WP.cam_shared = 0;
+    WP.cam_miss_once = 0;
     // (not for frame groups of one frame each: their blends must run in frame order)
     WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
     plan.slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
@@ -1392,6 +1397,20 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
 #endif
     const bool bulk = slots > c->finish_slots && !WP.fuse_blend;
     const bool cam = RT_CAM_SHADE && bulk && WP.cam_n && WP.n_frames >= 64;
+    if (pass == 0) {
+      // the groups that run both the shared camera trace and the CAM shade: miss pixels get their
+      // record and the hit pixels their list before the shade (wf_cam_classify: neither a trace nor
+      // a render launch in rt_stats); the flag stays set for the group's wf_blend
+      bool miss_once = RT_CAM_MISS_ONCE && cam && cam_shared;
+      if (const char* e = knob("RT_CAM_MISS_ONCE")) miss_once = miss_once && atoi(e) != 0;  // (A/B)
+      WP.cam_miss_once = miss_once ? 1 : 0;
+      if (miss_once) {
+        // (two blocks per CU: few waves, so few atomics on the list's counter)
+        hipLaunchKernelGGL(rtd::wf_cam_classify, dim3(std::max(1u, std::min<unsigned int>(2u * (unsigned)c->n_cus, (WP.K.n_work + 255u) / 256u))),
+                           dim3(256), 0, st, WP);
+        HIPCHK(c, hipGetLastError());
+      }
+    }
     launch_shade(bsdf, WP.fuse_blend ? ShadeKind::fused : cam ? ShadeKind::cam : bulk ? ShadeKind::bulk : ShadeKind::plain,
                  slots, st, WP);
     HIPCHK(c, hipGetLastError());

@@ -13,6 +13,11 @@
 //              then the next bounce's light sample, DisneySample, media and DisneyEval
 //              (RT:1376-1474); finished paths blend into the accumulation (RT:1552)
 //
+//   wf_cam_classify  (bulk groups of >= 64 frames, after the shared camera trace) per pixel: a
+//              camera miss's colour, once for all its frames, or an entry in the group's hit-pixel
+//              list; pass 0's shade then runs over the hit pixels' frames only and wf_blend takes a
+//              miss pixel's samples from that record (WFParams::cam_miss_once)
+//
 // wf_trace + wf_shade repeat maxBounce+1 times; passes with no work exit at once.  All frames
 // of one launch are in flight together (path slot = pixel * n_frames + frame): a pixel's frames
 // are independent until the progressive blend, so wf_blend applies RT:1552 afterwards in frame
@@ -64,7 +69,11 @@ struct WFState {
   // per work item: the camera hit point of its pixel (pass 0's shade, frame 0 of each pixel).  All
   // of a pixel's frames share it (R6: the camera ray is the same in every frame), so the rays that
   // pass 0 queues are stored as 16 B: {d.xyz, s} in ra / sa, origin = org + cam.xyz * s (s = the
-  // medium scattering distance of a continuation, else 0) instead of {o.xyz, d.x} + {d.y, d.z}
+  // medium scattering distance of a continuation, else 0) instead of {o.xyz, d.x} + {d.y, d.z}.
+  // With WFParams::cam_miss_once the row is the pixel's pass-0 record, written for every work item
+  // of every group by wf_cam_classify: {the camera miss's colour, 1} for a pixel whose camera ray
+  // leaves the scene (wf_blend reads it), .w = 0 for a hit pixel, whose frame 0 then stores the hit
+  // point with .w = 0 (the flag stays clear)
   float4* __restrict__ org;
   int* queue[2];                // ray queue entries: path << 1 | is_shadow
   int* queue_s[2];              // split queues (WFParams::split): the shadow rays, queue[k] + slots
@@ -83,6 +92,9 @@ constexpr int kFlagNoRayHist = 1 << 30;  // (internal, development builds) KPara
 __host__ __device__ constexpr unsigned int cq(unsigned int i) { return i; }
 __host__ __device__ constexpr unsigned int ca(unsigned int i) { return 2u + i; }
 constexpr unsigned int kCntFetch = 4u;
+// hit pixels of the group's camera pass (wf_cam_classify appends, wf_shade<..., CAM> reads): a line
+// of its own among the unused words, zeroed with the others by wf_camera
+constexpr unsigned int kCntHit = 32u;
 __host__ __device__ constexpr unsigned int xcnt(unsigned int s) { return 160u + 32u * s; }
 // split queues (WFParams::split): the shadow-ray queue counts of the two parities, and the claim
 // counters of its 8 segments (the continuation queue keeps cq / xcnt)
@@ -159,6 +171,13 @@ struct WFParams {
   // and each secondary pass traces them in two launches, wf_trace<..., KIND = 2> and <..., 1>.
   // split: this pass's rays are in split queues; split_out: the shade queues the next pass's apart
   int split, split_out;
+  // bulk groups whose pass 0 runs the shared camera trace and wf_shade<..., CAM>: a camera miss is
+  // the same sample in every frame (no jitter, R6: the environment colour of the direction, whatever
+  // the seed), so wf_cam_classify stores it once per pixel (WFState::org) and lists the hit pixels
+  // (S.active[0], unused in pass 0: the camera paths are implicit; count S.cnt[kCntHit]); the CAM
+  // shade runs over the listed pixels' frames only and wf_blend blends a miss pixel from its record.
+  // Set in pass 0 and left for the group's wf_blend
+  int cam_miss_once;
 };
 
 // Map a work index of this rank to (pixel, accumulation index); false outside the frame.
@@ -316,6 +335,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void w
       const float4 h = P.accum[ai];
       acc = mk3(h.x, h.y, h.z);
     }
+    // WFParams::cam_miss_once: a pixel whose camera ray missed has no fin rows; every frame's sample
+    // is its record's colour (WFState::org), blended by the same chain with the same weights.
+    // lmask: the miss flags of the 8 pixels whose rows this thread loads (p = i / BL_FR below);
+    // their loads go to clamp_row, frame 0 of one of the block's hit pixels (a written row, the same
+    // address for the whole block)
+    f3 mcol = splat(0.0f);
+    bool miss = false;
+    unsigned int lmask = 0u;
+    size_t clamp_row = 0;
+    if (W.cam_miss_once) {  // (uniform)
+      __shared__ unsigned char lmiss[256];
+      __shared__ unsigned int lhit;
+      if (valid) {
+        const float4 o = S.org[w];
+        miss = o.w != 0.0f;
+        mcol = mk3(o.x, o.y, o.z);
+      }
+      lmiss[threadIdx.x] = miss || !valid;
+      if (valid && !miss) lhit = w;  // (any of them)
+      if (__syncthreads_and(miss || !valid)) {  // no fin row under this block: no loads, no staging
+        if (valid) {
+          for (unsigned int f = 0; f < nf; f++) {
+            const float2 bw = P.blend_w[f];
+            acc = bw.x * mcol + bw.y * acc;
+          }
+          P.accum[ai] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+        }
+        continue;  // (nobody read lmiss / lhit)
+      }
+#pragma unroll
+      for (int j = 0; j < BL_FR; j++) lmask |= (unsigned int)lmiss[(threadIdx.x + 256u * (unsigned)j) / BL_FR] << j;
+      clamp_row = (size_t)lhit * nf;
+    }
     {
       static_assert(BL_FR == 8, "eight named registers");
       // (unconditional loads from a clamped index: a branch around each load would make the
@@ -326,8 +378,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void w
       auto ld1 = [&](unsigned int f0, int j) {
         const unsigned int nfc = min((unsigned int)BL_FR, nf - f0);
         const unsigned int i = threadIdx.x + 256u * (unsigned)j, p = i / BL_FR, k = i % BL_FR;
-        const bool ok = base + p < P.n_work && k < nfc;
-        return S.fin[ok ? (size_t)(base + p) * nf + f0 + k : 0];
+        const bool ok = base + p < P.n_work && k < nfc && !((lmask >> j) & 1u);
+        return S.fin[ok ? (size_t)(base + p) * nf + f0 + k : clamp_row];
       };
       auto st1 = [&](int j, float4 v) {
         const unsigned int i = threadIdx.x + 256u * (unsigned)j, p = i / BL_FR, k = i % BL_FR;
@@ -357,7 +409,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void w
           for (int k = 0; k < BL_FR; k++) {
             if ((unsigned)k < nfc) {
               const float4 c = tile[threadIdx.x * BL_PITCH + k];
-              acc = bw[k].x * xyz(c) + bw[k].y * acc;
+              acc = bw[k].x * (miss ? mcol : xyz(c)) + bw[k].y * acc;
             }
           }
       }
@@ -1485,6 +1537,9 @@ RTD HitGeom hit_geom(const KParams& P, int tri, f3 ro, f3 rd) {
 // lobe weights, the VNDF frame, the V-side Fresnel and masking terms).  The record is built from
 // the pixel's one camera trace result (WFParams::cam_shared: frame 0's slot; without it every
 // frame traces the same ray to the same closest hit, and the record still reads frame 0's).
+// With WFParams::cam_miss_once the block-iteration's pixels come from the group's hit-pixel list
+// (wf_cam_classify), every record is a hit and the miss branch below serves only the groups without
+// the list (counting runs, tile-cost probes, the A/B switch).
 // The other instantiations carry none of it (a
 // runtime record path in them cost the later passes' shades 2 ms per 256-frame group).
 constexpr int kCamRec = 11;  // [0..6] the hit, [7..10] v_terms
@@ -1516,6 +1571,69 @@ RTD void cam_rec(const WFParams& W, const Env& E, unsigned int w, float4* rec) {
     rec[1] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(r));
     rec[2] = make_float4(env.x, env.y, env.z, 0.0f);
   }
+}
+// WFParams::cam_miss_once, after the group's shared camera trace: one thread per work item reads
+// its pixel's one result.  A miss is the same sample in every frame, cam_rec's miss branch on the
+// same direction: its colour goes to the pixel's record (WFState::org, .w = 1) and its n_frames
+// samples are counted here; a hit pixel's flag is cleared and the pixel appended to the group's
+// hit list (S.active[0], S.cnt[kCntHit]; a wave-aggregated append, any order: no result depends on it), the work of
+// wf_shade<..., CAM>.  Every work item's record is written by every group: an earlier call from
+// another camera leaves other flags.
+__global__ __launch_bounds__(256) void wf_cam_classify(const WFParams W) {
+  const KParams& P = W.K;
+  const WFState& S = W.S;
+  const Env E{P.hdr, P.cache, P.light, P.hdr_w, P.hdr_h, P.hdr_res, P.env_angle, P.env_intensity};
+  const unsigned int nfr = (unsigned int)W.n_frames;
+  unsigned long long nsamples = 0;
+  // The append is aggregated per wave over up to 32 of its iterations (a chunk): the hit flags of
+  // the chunk in a register, one atomic for the wave's hits of the chunk, then the entries.  One
+  // atomic per wave and iteration (wave_append) puts 32 k atomics of a 1080p group on one counter
+  // line, ~11 ns each; this form issues ~2 k.  Shortest launch of a bench step 222 -> 75 us (the
+  // average, 0.94 -> 0.80 ms, is set by the other group's kernels it runs beside; the whole step
+  // is the same within noise: profiles/r08_C3_kernel_stats_wave_append.csv against
+  // r08_C3_kernel_stats.csv, r08_ab_cam_miss_once_wave_append_C3.log)
+  const unsigned int stride = gridDim.x * 256u, lane = threadIdx.x & 63u;
+  for (unsigned int c0 = blockIdx.x * 256u; c0 < P.n_work; c0 += 32u * stride) {  // (wave-uniform)
+    unsigned int hits = 0u, wcount = 0u;  // bit k: iteration k's work item is a hit; the wave's hits
+    for (unsigned int k = 0; k < 32u && c0 + k * stride < P.n_work; k++) {
+      const unsigned int w = c0 + k * stride + threadIdx.x;
+      const bool valid = w < P.n_work;
+      int r = valid ? S.res[2 * ((size_t)w * nfr)] : -1;
+#ifdef RT_CHECK
+      if (r >= P.n_tri) r = -1;  // (as cam_rec)
+#endif
+      const bool hit = valid && r >= 0;
+      if (hit) {
+        hits |= 1u << k;
+      } else if (valid) {
+        const f3 rd = xyz(S.cam[w]);
+        const f3 env = P.enable_env ? hdrColor(E, rd) * E.intensity : getDefaultSkyColor(rd.y);
+        S.org[w] = make_float4(env.x, env.y, env.z, 1.0f);
+        nsamples += nfr;
+      }
+      wcount += (unsigned int)__popcll(__ballot(hit));
+    }
+    unsigned int slot = 0u;
+    if (wcount) {
+      if (lane == 0u) slot = atomicAdd(&S.cnt[kCntHit], wcount);
+      slot = (unsigned int)__shfl((int)slot, 0);
+    }
+    for (unsigned int k = 0; k < 32u && c0 + k * stride < P.n_work; k++) {
+      const unsigned int w = c0 + k * stride + threadIdx.x;
+      const bool hit = (hits >> k) & 1u;
+      const unsigned long long m = __ballot(hit);
+      if (hit) {
+        S.active[0][slot + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = (int)w;
+        // (the flag alone: the frame groups of a batch share the table, and another group's pass 1 may
+        // be reading the hit point its frame 0 stored; every group writes the same flag and colour)
+        S.org[w].w = 0.0f;
+      }
+      slot += (unsigned int)__popcll(m);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) nsamples += __shfl_xor(nsamples, off);
+  if ((threadIdx.x & 63) == 0 && nsamples)
+    atomicAdd(&P.stats[stats_shard(blockIdx.x * 4u + (threadIdx.x >> 6)) + 1u], nsamples);
 }
 RTD BsdfFrame rec_frame(const float4* rec) {
   const float4 q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6];
@@ -1894,9 +2012,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   __shared__ unsigned int lc[6];  // queue count (shadow rays), active count, queue base, active base, continuations, (split) their base
   constexpr unsigned int kRecs = 256u * SH_SUB / 64u + 1u;  // pixels a block-iteration spans at >= 64 frames
   __shared__ float4 lrec[CAM ? kCamRec * kRecs : 1];
+  // CAM: the record of each staged path (its pixel's position among the block-iteration's pixels),
+  // so the shade loop below runs no division for it
+  __shared__ unsigned char lpos[CAM ? 256 * SH_SUB : 1];
   // 4 waves/SIMD = 4 blocks per CU: the block's LDS must fit a quarter of the CU's 160 KB
-  static_assert(4 * (2 * 256 * SH_SUB + 2 * 256 * SH_SUB) + 16 * (CAM ? kCamRec * kRecs : 1) +
-                    8 * SH_KEYS + 20 <= 40960,
+  static_assert(kRecs <= 256u, "lpos holds a byte per path");
+  static_assert(4 * (2 * 256 * SH_SUB + 2 * 256 * SH_SUB) + 16 * (CAM ? kCamRec * kRecs : 1) + (CAM ? 256 * SH_SUB : 1) +
+                    8 * SH_KEYS + 24 <= 40960,
                 "wf_shade LDS exceeds a quarter of the CU");
   const KParams& P = W.K;
   const WFState& S = W.S;
@@ -1905,6 +2027,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   constexpr bool camrec = CAM;
   const unsigned int na = CAM || W.cam_n ? W.cam_n : S.cnt[ca(in)];
   const unsigned int nq_in = CAM || W.cam_n ? W.cam_n : S.cnt[cq(in)] + (W.split ? S.cnt[cqs(in)] : 0u);
+  // WFParams::cam_miss_once: the paths to shade are the frames of the listed hit pixels, item j =
+  // frame j % nfr of pixel S.active[0][j / nfr] (wf_cam_classify; the device count bounds the loop);
+  // the counters below still count all cam_n camera paths, the reference's work
+  const bool once = CAM && W.cam_miss_once;
+  const unsigned int n_items = once ? S.cnt[kCntHit] * nfr : na;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     S.cnt[kCntFetch] = 0u;  // fetch counter of the next trace pass
     if (na) {
@@ -1920,7 +2047,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     nrays = nq_in;  // rays traced by the pass before us
     if (W.pass == 1 && W.p1_compact && nq_in) atomicAdd(&P.stats[17], (unsigned long long)nq_in);  // rt_stats.p1_rays
   }
-  for (unsigned int base = blockIdx.x * (256u * SH_SUB); base < na; base += gridDim.x * (256u * SH_SUB)) {
+  for (unsigned int base = blockIdx.x * (256u * SH_SUB); base < n_items; base += gridDim.x * (256u * SH_SUB)) {
   // ---- group the block's paths by what they will execute (block-local counting sort in LDS):
   // divergence between a continuation that missed (env lookup) and one that hit (a full BSDF
   // bounce) or between materials otherwise idles most lanes of a wave.  Order never changes a
@@ -1928,7 +2055,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   // Only for big secondary passes: the key loads add a dependent-latency step that small,
   // latency-bound late passes feel more than their divergence; the camera pass (lane
   // utilisation ~0.8) loses more than it gains (measured on C3, 64 frames in flight).
-  const unsigned int nblk = min(256u * SH_SUB, na - base);
+  const unsigned int nblk = min(256u * SH_SUB, n_items - base);
   if (threadIdx.x < SH_KEYS) lhist[threadIdx.x] = 0u;
   if (threadIdx.x == 0) lc[0] = lc[1] = lc[4] = 0u;
   __syncthreads();
@@ -1939,11 +2066,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
 #pragma unroll
     for (int sub = 0; sub < SH_SUB; sub++) {
       const unsigned int j = (unsigned)sub * 256u + threadIdx.x;
-      if (j < nblk) lsort[j] = CAM || W.cam_n ? (int)(base + j) : S.active[in][base + j];
+      if (j < nblk) {
+        if (CAM) {
+          const unsigned int q = (base + j) / nfr;
+          lsort[j] = once ? (int)((unsigned)S.active[0][q] * nfr + (base + j - q * nfr)) : (int)(base + j);
+          lpos[j] = (unsigned char)(q - base / nfr);
+        } else {
+          lsort[j] = W.cam_n ? (int)(base + j) : S.active[in][base + j];
+        }
+      }
     }
-    if (camrec) {  // the block-iteration's pixels' camera hits, one lane each
+    if (camrec) {  // the block-iteration's pixels' camera hits, one lane each (record = list position - p0)
       const unsigned int p0 = base / nfr, np = (base + nblk - 1u) / nfr - p0 + 1u;
-      if (threadIdx.x < np) cam_rec(W, E, p0 + threadIdx.x, lrec + kCamRec * threadIdx.x);
+      if (threadIdx.x < np) cam_rec(W, E, once ? (unsigned)S.active[0][p0 + threadIdx.x] : p0 + threadIdx.x, lrec + kCamRec * threadIdx.x);
     }
   } else {
   int skey[SH_SUB], srank[SH_SUB], spath[SH_SUB];
@@ -1972,9 +2107,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     const unsigned int jj = (unsigned)sub * 256u + threadIdx.x;
     const bool live = jj < nblk;
     int path = live ? lsort[jj] : 0;
-    // (an idle lane's pointer is out of range and never read: shade_path reads rec only for live
-    // paths; clamping it cost the CAM kernel 12 B of scratch)
-    const float4* rec = camrec ? lrec + kCamRec * ((unsigned)path / nfr - base / nfr) : nullptr;
+    // (an idle lane reads the position of an earlier block-iteration or none: a record inside lrec
+    // or not, never read, as shade_path reads rec only for live paths)
+    const float4* rec = camrec ? lrec + kCamRec * lpos[jj] : nullptr;
     const ShadeOut so = shade_path<BSDF, FUSE, CAM>(W, E, path, live, CAM || W.cam_n != 0, !CAM && W.pass != 0, nsamples, rec);
     const bool qShadow = so.qShadow, qCont = so.qCont, keep = qShadow || qCont;
     // shadow rays from the front of the block's staging list, continuations from the back: the
