@@ -84,10 +84,22 @@ int dev_pass_report(rt_ctx* c, hipStream_t st, const rtd::WFParams& WP, int g, i
   HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
   HIPCHK(c, hipMemcpy(h, c->d_stats, sizeof(h), hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(q, WP.S.cnt, sizeof(q), hipMemcpyDeviceToHost));
+  const unsigned int n_cont = q[rtd::cq(pass & 1)], n_shadow = q[rtd::cqs(pass & 1)], n_kept = q[rtd::ca(pass & 1)];
   q[0] = q[rtd::cq(pass & 1)] + (WP.split ? q[rtd::cqs(pass & 1)] : 0u);  // (split queues: both kinds)
   const unsigned int traced = WP.cam_n ? (WP.cam_shared ? WP.K.n_work : WP.cam_n) : q[0];  // traversals of the launch
   fprintf(stderr, "[rt] group %d pass %d: %u rays %.3f ms  cum internal %llu leaf %llu tri %llu iters %llu "
           "wave-iters max %llu ray-steps max %llu\n", g, pass, traced, ms, h[2], h[3], h[4], h[5], h[6], h[7]);
+  if (!WP.cam_n) {
+    // the pass's lists as the shade before it counted them (with WFParams::p1_lean pass 1 has no
+    // continuation queue or active list: its continuation trace and shade walk the hit-pixel list,
+    // `items` entries, and these are counts alone)
+    unsigned int hits = 0;
+    HIPCHK(c, hipMemcpy(&hits, WP.S.cnt + rtd::kCntHit, sizeof(hits), hipMemcpyDeviceToHost));
+    const bool lean1 = WP.p1_lean && pass == 1;
+    fprintf(stderr, "[rt]   lists: continuations %u shadow rays %u kept paths %u  p1_lean %d items %u\n",
+            WP.split ? n_cont : 0u, WP.split ? n_shadow : 0u, n_kept, lean1 ? 1 : 0,
+            lean1 ? hits * (unsigned)WP.n_frames : n_kept);
+  }
   unsigned long long hq[6];
   HIPCHK(c, hipMemcpy(hq, c->d_stats + 22, sizeof(hq), hipMemcpyDeviceToHost));
   fprintf(stderr, "[rt]   4-wide node visits with BFS index < 1 / 5 / 21 / 64 / 85 / 341: %llu %llu %llu %llu %llu %llu\n",

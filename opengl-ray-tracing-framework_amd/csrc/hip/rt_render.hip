@@ -60,6 +60,9 @@ struct rt_ctx {
   bool scene_set = false;
   std::vector<int32_t> tri_mat;  // host copy of the per-triangle material ids (for updates)
   std::vector<float> mat_table;  // host copy, 32 floats per material
+  // some material's emission is not +0 (all bits): an emissive camera hit needs s2.w for Le0.y, so
+  // such scenes keep the full pass-0 -> pass-1 state (WFParams::p1_lean stays 0)
+  bool mats_emissive = false;
   // env
   float4* d_hdr = nullptr;
   float2* d_cache = nullptr;                  // hdrCache.rg; d_hdr = {hdrMap.rgb, hdrCache.b}
@@ -135,6 +138,11 @@ struct rt_ctx {
                           // camera ray misses once per group, not once per frame (WFParams::cam_miss_once)
 #define RT_CAM_MISS_ONCE 1
 #endif
+#ifndef RT_P1_LEAN  // groups with cam_miss_once and 16-B pass-1 rays in a scene without emissive materials: pass 1
+                    // walks the hit-pixel list (no s5 row, active list or continuation queue out of pass 0:
+                    // WFParams::p1_lean)
+#define RT_P1_LEAN 1
+#endif
 #ifndef RT_CAM_SHARED_STATIC  // a bulk group's shared camera trace (one ray per work item: a small pass) runs the
                               // bulk's instantiation (0) or the small passes' (1: static shares, lane quads, every
                               // claim 64 rays): C3, 2.07 M rays of one 256-frame group standalone 0.299 vs 0.662 ms
@@ -160,6 +168,7 @@ struct rt_ctx {
   // wavefront path state (one slot per local pixel)
   void* wf_mem = nullptr;
   size_t wf_paths = 0;                        // path slots per frame group
+  size_t wf_hit_cap = 0;                      // entries of each set's hit-pixel list (WFState::hit)
   rtd::WFState wf{};                          // pixel lists (shared by every group)
   // Frame groups: the frames of one batch are split into n_groups independent wavefronts with
   // their own path state, run on their own streams, so the latency tail of one group's late
@@ -238,6 +247,15 @@ namespace {
 // tests/test_gpu_cull.py (RT_CULL_EPS_SCALE), the traversal-structure variants the parity tests
 // cover (RT_BVH_WIDTH, RT_REBUILD, RT_COLLAPSE, RT_QBFS) and the occupancy / grouping / finisher
 // parameters the A/B tools sweep.
+// rt_ctx::mats_emissive of a material table (32 floats per material, the emission first)
+inline bool table_emissive(const std::vector<float>& t) {
+  for (size_t k = 0; k + 32 <= t.size(); k += 32) {
+    uint32_t b[3];
+    memcpy(b, &t[k], sizeof(b));
+    if (b[0] | b[1] | b[2]) return true;
+  }
+  return false;
+}
 inline const char* knob(const char* name) {
 #ifdef RT_DEV
   return getenv(name);
@@ -405,6 +423,7 @@ void launch_trace_w(rt_ctx* c, dim3 grid, const rtd::WFParams& WP, hipStream_t s
     for (int k = 0; k < 2; k++) {
       const bool shadow = (k == 0) != (RT_SPLIT_CONT_FIRST != 0);
       if (p1 && shadow) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, true, 2>), grid, dim3(256), c->trace_lds, st, WP);
+      else if (p1 && WP.p1_lean) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, true, 1, true>), grid, dim3(256), c->trace_lds, st, WP);
       else if (p1) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, true, 1>), grid, dim3(256), c->trace_lds, st, WP);
       else if (shadow) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 2>), grid, dim3(256), c->trace_lds, st, WP);
       else hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 1>), grid, dim3(256), c->trace_lds, st, WP);
@@ -436,18 +455,21 @@ void launch_trace(rt_ctx* c, bool count, dim3 grid, const rtd::WFParams& WP, hip
 // inside the shade (WFParams::fuse_blend); bulk: groups above finish_slots, RT_SH_SUB_BULK paths
 // per thread and block-iteration; cam: the camera pass of a bulk group with >= 64 frames
 // (camera-hit records); plain: everything else
-enum class ShadeKind { plain, bulk, cam, fused };
+// cam_lean / bulk_lean: pass 0 / pass 1 of a group with WFParams::p1_lean (the LEAN instantiations)
+enum class ShadeKind { plain, bulk, cam, fused, cam_lean, bulk_lean };
 template <bool BSDF>
 void launch_shade_t(ShadeKind kind, dim3 grid, hipStream_t st, const rtd::WFParams& WP) {
   if (kind == ShadeKind::fused) hipLaunchKernelGGL((rtd::wf_shade<BSDF, true>), grid, dim3(256), 0, st, WP);
   else if (kind == ShadeKind::cam) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_CAM, true>), grid, dim3(256), 0, st, WP);
+  else if (kind == ShadeKind::cam_lean) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_CAM, true, true>), grid, dim3(256), 0, st, WP);
+  else if (kind == ShadeKind::bulk_lean) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_BULK, false, true>), grid, dim3(256), 0, st, WP);
   else if (kind == ShadeKind::bulk) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_BULK>), grid, dim3(256), 0, st, WP);
   else hipLaunchKernelGGL((rtd::wf_shade<BSDF, false>), grid, dim3(256), 0, st, WP);
 }
 void launch_shade(bool bsdf, ShadeKind kind, unsigned int slots, hipStream_t st, const rtd::WFParams& WP) {
-  const unsigned int sub = kind == ShadeKind::cam    ? (unsigned)rtd::SH_SUB_CAM
-                           : kind == ShadeKind::bulk ? (unsigned)rtd::SH_SUB_BULK
-                                                     : (unsigned)rtd::SH_SUB;
+  const unsigned int sub = kind == ShadeKind::cam || kind == ShadeKind::cam_lean    ? (unsigned)rtd::SH_SUB_CAM
+                           : kind == ShadeKind::bulk || kind == ShadeKind::bulk_lean ? (unsigned)rtd::SH_SUB_BULK
+                                                                                      : (unsigned)rtd::SH_SUB;
   const dim3 grid(std::max(1u, std::min<unsigned int>(4096u, (slots + 256u * sub - 1) / (256u * sub))));
   if (bsdf) launch_shade_t<true>(kind, grid, st, WP);
   else launch_shade_t<false>(kind, grid, st, WP);
@@ -579,7 +601,9 @@ int alloc_wavefront(rt_ctx* c, size_t paths) {
     c->wf_mem = nullptr;
   }
   const size_t P = std::max<size_t>(paths, 64);
-  const size_t per = P * (5 * 16 + sizeof(*c->wfg[0].s5) + 2 * (16 + 8) + 2 * 4 + 16 + 2 * 8 + 2 * 4) + 32768;  // + carve padding
+  // the hit-pixel list: one entry per work item of a group of >= 64 frames (wf_cam_classify)
+  const size_t hit_cap = P / 64 + 64;
+  const size_t per = P * (5 * 16 + sizeof(*c->wfg[0].s5) + 2 * (16 + 8) + 2 * 4 + 16 + 2 * 8 + 2 * 4) + hit_cap * 4 + 32768;  // + carve padding
   const hipError_t me = hipMalloc(&c->wf_mem, per * c->n_groups);
   if (me == hipErrorOutOfMemory) {
     (void)hipGetLastError();
@@ -601,9 +625,11 @@ int alloc_wavefront(rt_ctx* c, size_t paths) {
     w.queue[0] = (int*)carve(P * 8); w.queue[1] = (int*)carve(P * 8);
     w.queue_s[0] = w.queue[0] + P; w.queue_s[1] = w.queue[1] + P;  // (split queues: one entry per path each)
     w.active[0] = (int*)carve(P * 4); w.active[1] = (int*)carve(P * 4);
+    w.hit = (int*)carve(hit_cap * 4);
     w.cnt = (unsigned int*)carve(rtd::kCntWords * 4);
   }
   c->wf_paths = P;
+  c->wf_hit_cap = hit_cap;
   return RT_OK;
 }
 
@@ -727,6 +753,7 @@ int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   c->qstack_entries = std::max(2, 3 * k.qdepth + 2);
   c->tri_mat = std::move(k.tri_mat);
   c->mat_table = std::move(k.mats);
+  c->mats_emissive = table_emissive(c->mat_table);
   c->scene_set = true;
   return occupancy(c);
 }
@@ -754,6 +781,7 @@ int rt_update_materials(rt_ctx* c, int32_t first, int32_t count, const rt_materi
     c->mat_table.resize(32 * (size_t)(id + 1));
     memcpy(&c->mat_table[32 * id], packed, sizeof(packed));
     c->n_mats++;
+    c->mats_emissive = table_emissive(c->mat_table);
     int rc = upload(c, (void**)&c->d_mats, c->mat_table.data(), c->mat_table.size() * sizeof(float));
     if (rc) return rc;
   }
@@ -1299,6 +1327,7 @@ int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, co
     WP.cam_n = 0u;
     WP.cam_shared = 0;
     WP.cam_miss_once = 0;
+    WP.p1_lean = 0;
     // (not for frame groups of one frame each: their blends must run in frame order)
     WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
     plan.slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
@@ -1401,9 +1430,14 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
       // the groups that run both the shared camera trace and the CAM shade: miss pixels get their
       // record and the hit pixels their list before the shade (wf_cam_classify: neither a trace nor
       // a render launch in rt_stats); the flag stays set for the group's wf_blend
-      bool miss_once = RT_CAM_MISS_ONCE && cam && cam_shared;
+      bool miss_once = RT_CAM_MISS_ONCE && cam && cam_shared && WP.K.n_work <= c->wf_hit_cap;
       if (const char* e = knob("RT_CAM_MISS_ONCE")) miss_once = miss_once && atoi(e) != 0;  // (A/B)
       WP.cam_miss_once = miss_once ? 1 : 0;
+      // the lean pass-0 -> pass-1 state: pass 1 exists, reads 16-B rays and split queues, and no
+      // camera hit can be emissive
+      bool lean = RT_P1_LEAN && miss_once && WP.p1_compact && last_pass >= 1 && WP.split_out && !c->mats_emissive;
+      if (const char* e = knob("RT_P1_LEAN")) lean = lean && atoi(e) != 0;  // (A/B)
+      WP.p1_lean = lean ? 1 : 0;
       if (miss_once) {
         // (two blocks per CU: few waves, so few atomics on the list's counter)
         hipLaunchKernelGGL(rtd::wf_cam_classify, dim3(std::max(1u, std::min<unsigned int>(2u * (unsigned)c->n_cus, (WP.K.n_work + 255u) / 256u))),
@@ -1411,7 +1445,9 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
         HIPCHK(c, hipGetLastError());
       }
     }
-    launch_shade(bsdf, WP.fuse_blend ? ShadeKind::fused : cam ? ShadeKind::cam : bulk ? ShadeKind::bulk : ShadeKind::plain,
+    const bool lean0 = WP.p1_lean && pass == 0, lean1 = WP.p1_lean && pass == 1;
+    launch_shade(bsdf, WP.fuse_blend ? ShadeKind::fused : lean0 ? ShadeKind::cam_lean : cam ? ShadeKind::cam
+                       : lean1 ? ShadeKind::bulk_lean : bulk ? ShadeKind::bulk : ShadeKind::plain,
                  slots, st, WP);
     HIPCHK(c, hipGetLastError());
   }

@@ -78,6 +78,10 @@ struct WFState {
   int* queue[2];                // ray queue entries: path << 1 | is_shadow
   int* queue_s[2];              // split queues (WFParams::split): the shadow rays, queue[k] + slots
   int* active[2];               // active path ids
+  // the group's hit-pixel list (wf_cam_classify; count cnt[kCntHit]): one work item per entry, any
+  // order.  A buffer of its own: with WFParams::p1_lean pass 1's kernels still walk it while that
+  // pass's shade writes active[0]
+  int* __restrict__ hit;
   unsigned int* __restrict__ cnt;  // queue counts, active counts, trace fetch, segment claims (cq, ca, ... below)
 };
 
@@ -92,8 +96,9 @@ constexpr int kFlagNoRayHist = 1 << 30;  // (internal, development builds) KPara
 __host__ __device__ constexpr unsigned int cq(unsigned int i) { return i; }
 __host__ __device__ constexpr unsigned int ca(unsigned int i) { return 2u + i; }
 constexpr unsigned int kCntFetch = 4u;
-// hit pixels of the group's camera pass (wf_cam_classify appends, wf_shade<..., CAM> reads): a line
-// of its own among the unused words, zeroed with the others by wf_camera
+// hit pixels of the group's camera pass (wf_cam_classify appends to WFState::hit; wf_shade<..., CAM>
+// and, with WFParams::p1_lean, pass 1's continuation trace and shade read): a line of its own among
+// the unused words, zeroed with the others by wf_camera
 constexpr unsigned int kCntHit = 32u;
 __host__ __device__ constexpr unsigned int xcnt(unsigned int s) { return 160u + 32u * s; }
 // split queues (WFParams::split): the shadow-ray queue counts of the two parities, and the claim
@@ -174,10 +179,21 @@ struct WFParams {
   // bulk groups whose pass 0 runs the shared camera trace and wf_shade<..., CAM>: a camera miss is
   // the same sample in every frame (no jitter, R6: the environment colour of the direction, whatever
   // the seed), so wf_cam_classify stores it once per pixel (WFState::org) and lists the hit pixels
-  // (S.active[0], unused in pass 0: the camera paths are implicit; count S.cnt[kCntHit]); the CAM
+  // (S.hit, count S.cnt[kCntHit]); the CAM
   // shade runs over the listed pixels' frames only and wf_blend blends a miss pixel from its record.
   // Set in pass 0 and left for the group's wf_blend
   int cam_miss_once;
+  // lean pass-0 -> pass-1 protocol (groups with cam_miss_once and p1_compact whose scene has no
+  // emissive material; the LEAN instantiations of wf_shade and wf_trace): pass 1's paths are the
+  // frames of the listed hit pixels in list order, item j = frame j % n_frames of S.hit[j / n_frames],
+  // as pass 0's are, so the CAM shade writes no active list, no continuation queue and no s5 row.
+  // A path's flag byte travels in s2.w (Le0.y, +0 after every non-emissive camera hit: PF_ZLO), 0 for
+  // a path that queued nothing; its seed is the camera seed advanced by the five draws of a camera
+  // bounce (lean_seed); its bounce is 0.  Every listed path has an ra row: all zeros without a
+  // continuation, which pass 1's continuation trace skips.  The shadow queue stays explicit (a
+  // sixth of the paths have no shadow ray), and cnt[cq] / cnt[ca] still receive the continuation
+  // and kept-path counts, so every statistic keeps its value
+  int p1_lean;
 };
 
 // Map a work index of this rank to (pixel, accumulation index); false outside the frame.
@@ -1164,9 +1180,14 @@ RTD int coop_move(TraceLane& L, const TraceStack& TS, unsigned long long live, i
 // KIND: 0 the pass's one queue (both kinds); with split queues (WFParams::split) 1 the
 // continuations (closest hit) and 2 the shadow rays (any hit: no culling, no child sort, AH
 // triangle test), each launch its own instantiation with no per-lane kind
-template <bool COUNT, bool WIDE, bool CAM, bool STATIC = false, bool P1 = false, int KIND = 0>  // P1: pass 1's 16-B rays
+// LEAN (WFParams::p1_lean; pass 1's continuation launch, P1 and KIND = 1): no queue; entry qi is
+// frame qi % n_frames of pixel S.hit[qi / n_frames], the division p1_ray runs anyway and one list
+// load shared by a pixel's frames; a path whose ra row is all zeros has no continuation and leaves
+// the lane idle until the next refill.  Its own instantiation: the explicit-queue kernel is unchanged
+template <bool COUNT, bool WIDE, bool CAM, bool STATIC = false, bool P1 = false, int KIND = 0, bool LEAN = false>  // P1: pass 1's 16-B rays
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRACE_WPE_DUAL)))
 void wf_trace(const WFParams W) {
+  static_assert(!LEAN || (P1 && KIND == 1 && !CAM && !COUNT), "the lean protocol's continuation trace");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const KParams& P = W.K;
   const WFState& S = W.S;
@@ -1174,7 +1195,10 @@ void wf_trace(const WFParams W) {
   constexpr bool AHK = KIND == 2;  // every ray of the launch is any-hit
   const bool shared = CAM && W.cam_shared;  // one camera ray per work item: entry i = slot i * n_frames
   const unsigned int cam_stride = shared ? (unsigned int)W.n_frames : 1u;
-  const unsigned int nq = CAM ? (shared ? P.n_work : W.cam_n) : AHK ? S.cnt[cqs(qin)] : S.cnt[cq(qin)];
+  const unsigned int nq = CAM    ? (shared ? P.n_work : W.cam_n)
+                          : LEAN ? S.cnt[kCntHit] * (unsigned int)W.n_frames
+                          : AHK  ? S.cnt[cqs(qin)]
+                                 : S.cnt[cq(qin)];
   const int* __restrict__ Q = AHK ? S.queue_s[qin] : S.queue[qin];
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // the shade pass after us appends here
     S.cnt[cq(qin ^ 1)] = 0u;
@@ -1182,7 +1206,8 @@ void wf_trace(const WFParams W) {
     S.cnt[ca(qin ^ 1)] = 0u;
   }
   if (nq == 0u || !P.has_scene) {
-    if (!P.has_scene) {  // empty scene: every ray misses (RT:346 reads a zero node)
+    // (LEAN: an empty scene has no hit pixel, so nq is 0 and there is no queue to walk)
+    if (!P.has_scene && !LEAN) {  // empty scene: every ray misses (RT:346 reads a zero node)
       for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
         const int e = CAM ? (int)((i * cam_stride) << 1) : Q[i];
         S.res[e] = -1;
@@ -1300,6 +1325,7 @@ void wf_trace(const WFParams W) {
         const unsigned int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
         if (!busy && rank < avail) {
           const unsigned int qi = pool_next + rank;
+          bool go = true;  // (LEAN: false for a path without a continuation)
           if (CAM) {  // implicit camera pass: queue entry i is slot i's camera ray, or work item i's
             const unsigned int slot = qi * cam_stride;
             entry = (int)(slot << 1);
@@ -1307,6 +1333,22 @@ void wf_trace(const WFParams W) {
             const float4 d = S.cam[shared ? qi : slot / (unsigned int)P.n_frames];
             L.ox = P.pos[0]; L.oy = P.pos[1]; L.oz = P.pos[2];
             L.dx = d.x; L.dy = d.y; L.dz = d.z;
+          } else if (LEAN) {  // frame qi % n of the listed pixel qi / n; origin as p1_ray
+            const unsigned int nf = (unsigned int)W.n_frames, li = qi / nf;
+            const unsigned int w = (unsigned int)S.hit[li], path = w * nf + (qi - li * nf);
+            const float4 oa = S.ra[path];
+            go = (__float_as_uint(oa.x) | __float_as_uint(oa.y) | __float_as_uint(oa.z) | __float_as_uint(oa.w)) != 0u;
+            if (go) {
+              entry = (int)(path << 1);
+              L.anyhit = false;
+              const float4 o = S.org[w];
+              L.ox = o.x; L.oy = o.y; L.oz = o.z;
+              if (oa.w != 0.0f) {
+                const float4 c = S.cam[w];
+                L.ox = o.x + c.x * oa.w; L.oy = o.y + c.y * oa.w; L.oz = o.z + c.z * oa.w;
+              }
+              L.dx = oa.x; L.dy = oa.y; L.dz = oa.z;
+            }
           } else {
             entry = Q[qi];
             const int path = entry >> 1;
@@ -1321,8 +1363,10 @@ void wf_trace(const WFParams W) {
               L.dx = oa.w; L.dy = ob.x; L.dz = ob.y;
             }
           }
-          tl_start<WIDE>(P, L);
-          busy = true;
+          if (!LEAN || go) {
+            tl_start<WIDE>(P, L);
+            busy = true;
+          }
         }
         pool_next += min((unsigned int)__popcll(idle), avail);
       }
@@ -1341,7 +1385,10 @@ void wf_trace(const WFParams W) {
         busy = (lane >> 2) < nl && b_src != 0;
       }
     }
-    if (!__any(busy)) break;
+    if (!__any(busy)) {
+      if (LEAN && !drained) continue;  // a refill of paths without a continuation: take the next entries
+      break;
+    }
     if (COUNT) { v_itO++; if (busy) v_busyO++; }
     bool finished = false;
     if (COUNT) { v_itN++; v_itT++; }
@@ -1468,8 +1515,10 @@ constexpr int SH_KEYS = 2;  // 0: no continuation hit (env / end of path); 1: a 
 
 // what a path's shade iteration will run: the cheap end-of-path / env branch or a bounce on
 // the hit material
+// LEAN (WFParams::p1_lean, pass 1): the flag byte is in s2.w; 0 (a path that queued nothing) has key 0
+template <bool LEAN = false>
 RTD int shade_key(const KParams& P, const WFState& S, int path) {
-  const uint32_t flags = S.s5[path].y & 0xffu;
+  const uint32_t flags = (LEAN ? __float_as_uint(S.s2[path].w) : S.s5[path].y) & 0xffu;
   const int t = S.res[2 * path];
   if (!(flags & PF_CONT) || t < 0) return 0;
   return 1;
@@ -1576,7 +1625,7 @@ RTD void cam_rec(const WFParams& W, const Env& E, unsigned int w, float4* rec) {
 // its pixel's one result.  A miss is the same sample in every frame, cam_rec's miss branch on the
 // same direction: its colour goes to the pixel's record (WFState::org, .w = 1) and its n_frames
 // samples are counted here; a hit pixel's flag is cleared and the pixel appended to the group's
-// hit list (S.active[0], S.cnt[kCntHit]; a wave-aggregated append, any order: no result depends on it), the work of
+// hit list (S.hit, S.cnt[kCntHit]; a wave-aggregated append, any order: no result depends on it), the work of
 // wf_shade<..., CAM>.  Every work item's record is written by every group: an earlier call from
 // another camera leaves other flags.
 __global__ __launch_bounds__(256) void wf_cam_classify(const WFParams W) {
@@ -1623,7 +1672,7 @@ __global__ __launch_bounds__(256) void wf_cam_classify(const WFParams W) {
       const bool hit = (hits >> k) & 1u;
       const unsigned long long m = __ballot(hit);
       if (hit) {
-        S.active[0][slot + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = (int)w;
+        S.hit[slot + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = (int)w;
         // (the flag alone: the frame groups of a batch share the table, and another group's pass 1 may
         // be reading the hit point its frame 0 stored; every group writes the same flag and colour)
         S.org[w].w = 0.0f;
@@ -1647,8 +1696,16 @@ RTD BsdfFrame rec_frame(const float4* rec) {
   return F;
 }
 
+// the seed a path leaves its camera bounce with: both integrators draw five numbers there (xa, xb,
+// cu, cv, xi_3), whatever they sample
+RTD uint32_t lean_seed(uint32_t cseed) {
+  for (int k = 0; k < 5; k++) (void)rand_(cseed);
+  return cseed;
+}
 // CAMK: the camera pass of wf_shade<..., CAM> (every path's hit from its pixel's record)
-template <bool BSDF, bool FUSE = false, bool CAMK = false>  // FUSE: W.fuse_blend is honoured (one-frame pixel groups)
+// LEAN (WFParams::p1_lean): with CAMK the writer of the lean pass-0 -> pass-1 state, else its reader
+// (pass 1 of such a group); both in instantiations of their own
+template <bool BSDF, bool FUSE = false, bool CAMK = false, bool LEAN = false>  // FUSE: W.fuse_blend is honoured (one-frame pixel groups)
 RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bool camPass, bool loadPrev,
                         unsigned long long& nsamples, const float4* rec = nullptr) {
   const KParams& P = W.K;
@@ -1672,6 +1729,10 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
       const f3 d = camera_ray(P, S, (unsigned)path, cseed, cframe);
       a5 = make_uint4(cseed, 0u, PF_CONT | PF_CAMERA, cframe);
       cam_d = make_float4(d.x, d.y, d.z, 0.0f);
+    } else if (LEAN) {  // bounce 0, the seed recomputed; the flags come with the s2 row below
+      uint32_t cseed, cframe;
+      (void)camera_ray(P, S, (unsigned)path, cseed, cframe);
+      a5 = make_uint4(lean_seed(cseed), 0u, 0u, cframe);
     } else {
       const uint2 p5 = S.s5[path];
       const unsigned int nfr = (unsigned int)W.n_frames;
@@ -1683,6 +1744,10 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
     if (loadPrev) {
       a0 = S.s0[path]; a2 = S.s2[path];
       rsh = S.res[2 * path + 1];
+      if (LEAN && !CAMK) {  // s2.w carries the flag byte; Le0.y is +0 (PF_ZLO: no emissive material)
+        a5.z = __float_as_uint(a2.w) & 0xffu;
+        a2.w = 0.0f;
+      }
       // (PF_ZLO) a path whose Lo and Le0 are +0 (every path after a non-emissive camera hit, whose
       // NEE is still pending) skips the s1 row and, without a shadow ray, the s3 row
       if (!(a5.z & PF_ZLO)) {
@@ -1703,7 +1768,7 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
     if (camPass) {
       oo0 = make_float4(P.pos[0], P.pos[1], P.pos[2], 0.0f);
       dd0 = make_float4(cam_d.x, cam_d.y, cam_d.z, 0.0f);
-    } else if (W.p1_compact && W.pass == 1) {  // (uniform) the continuation in pass 0's 16-B form
+    } else if ((LEAN && !CAMK) || (W.p1_compact && W.pass == 1)) {  // (uniform) the continuation in pass 0's 16-B form
       const float4 ra0 = S.ra[path];
       float ox, oy, oz;
       p1_ray(S, (unsigned)W.n_frames, (unsigned)path, ra0, ox, oy, oz);
@@ -1716,7 +1781,10 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
       dd0 = make_float4(ra0.w, rb0.x, rb0.y, 0.0f);
     }
     wseed = a5.x; bounce = a5.y; flags = a5.z; frame = a5.w;
-    if (!(flags & PF_CAMERA)) {
+    // (LEAN reader) flags 0: the path queued nothing in pass 0 and has finished there
+    const bool dead = LEAN && !CAMK && flags == 0u;
+    if (dead) {
+    } else if (!(flags & PF_CAMERA)) {
       hist = xyz(a0); evp = a0.w;
       Lo = xyz(a1);
       evf = xyz(a2);
@@ -1730,7 +1798,8 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
         Lo = Lo + xyz(a4);
       }
     }
-    if (!(flags & PF_CONT)) {  // BSDF pdf was 0 (RT:1460-1462): the path ends
+    if (dead) {
+    } else if (!(flags & PF_CONT)) {  // BSDF pdf was 0 (RT:1460-1462): the path ends
       fin = Le0 + Lo;
       doFinish = true;
     } else {
@@ -1977,7 +2046,21 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
 
   // ------------------------------------------------------------ enqueue rays
   const bool keep = qShadow || qCont;
-  if (keep) {
+  if (LEAN && CAMK) {  // the lean pass-0 -> pass-1 rows (WFParams::p1_lean) of a listed path: live is a camera hit
+    if (live) {
+      // (Lo and Le0 are +0 here: Lo starts the path, and no material of the scene is emissive)
+      if (keep) nflags |= PF_ZLO;
+      if (keep) st_row(S.s0 + path, make_float4(hist.x, hist.y, hist.z, evp));
+      st_row(S.s2 + path, make_float4(evf.x, evf.y, evf.z, __uint_as_float(keep ? nflags : 0u)));
+      if (qShadow) st_row(S.s3 + path, make_float4(cnee.x, cnee.y, cnee.z, 0.0f));
+      if (nflags & PF_CMED) st_row(S.s4 + path, make_float4(cmed.x, cmed.y, cmed.z, 0.0f));
+      if (!BSDF && qCont) st_row(S.s4 + path, make_float4(bNdotL, 0.0f, 0.0f, 0.0f));
+      // every listed path has an ra row: zeros without a continuation (never a ray: a sampled
+      // direction has unit length), which pass 1's continuation trace skips
+      if (qCont || P.max_bounce > 0) st_row(S.ra + path, qCont ? make_float4(contD.x, contD.y, contD.z, contS) : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+      if (qShadow) st_row(S.sa + path, make_float4(shD.x, shD.y, shD.z, 0.0f));
+    }
+  } else if (keep) {
     const bool zlo = (__float_as_uint(Lo.x) | __float_as_uint(Lo.y) | __float_as_uint(Lo.z) |
                                 __float_as_uint(Le0.x) | __float_as_uint(Le0.y) | __float_as_uint(Le0.z)) == 0u;
     if (zlo) nflags |= PF_ZLO;
@@ -2003,10 +2086,15 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
 // instantiation each so neither carries the other's registers
 // CAM: the bulk groups' camera pass (>= 64 frames per group, camera-hit records), its own
 // instantiation: no path state to load, so none of its registers
-template <bool BSDF, bool FUSE = false, int SH_SUB = rtd::SH_SUB, bool CAM = false>  // SH_SUB: paths per thread and block-iteration
+// LEAN (WFParams::p1_lean), instantiations of their own: with CAM the camera pass that leaves the lean
+// state (shadow queue only; the continuation and kept-path counts still go to cnt[cq] / cnt[ca]),
+// without CAM pass 1 of such a group, whose items are the listed hit pixels' frames as the CAM
+// shade's are; a path with flag byte 0 is skipped (shade_path)
+template <bool BSDF, bool FUSE = false, int SH_SUB = rtd::SH_SUB, bool CAM = false, bool LEAN = false>  // SH_SUB: paths per thread and block-iteration
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WPE))) void wf_shade(const WFParams W) {
-  __shared__ int lq[2 * 256 * SH_SUB];
-  __shared__ int la[256 * SH_SUB];
+  constexpr bool LEANW = LEAN && CAM, LEANR = LEAN && !CAM;  // the lean state's writer / reader
+  __shared__ int lq[(LEANW ? 1 : 2) * 256 * SH_SUB];  // (LEANW: shadow rays only)
+  __shared__ int la[LEANW ? 1 : 256 * SH_SUB];
   __shared__ int lsort[256 * SH_SUB];  // the block's paths, grouped by shade_key
   __shared__ unsigned int lhist[SH_KEYS], lofs[SH_KEYS];
   __shared__ unsigned int lc[6];  // queue count (shadow rays), active count, queue base, active base, continuations, (split) their base
@@ -2028,9 +2116,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   const unsigned int na = CAM || W.cam_n ? W.cam_n : S.cnt[ca(in)];
   const unsigned int nq_in = CAM || W.cam_n ? W.cam_n : S.cnt[cq(in)] + (W.split ? S.cnt[cqs(in)] : 0u);
   // WFParams::cam_miss_once: the paths to shade are the frames of the listed hit pixels, item j =
-  // frame j % nfr of pixel S.active[0][j / nfr] (wf_cam_classify; the device count bounds the loop);
+  // frame j % nfr of pixel S.hit[j / nfr] (wf_cam_classify; the device count bounds the loop);
   // the counters below still count all cam_n camera paths, the reference's work
-  const bool once = CAM && W.cam_miss_once;
+  const bool once = LEAN || (CAM && W.cam_miss_once);
   const unsigned int n_items = once ? S.cnt[kCntHit] * nfr : na;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     S.cnt[kCntFetch] = 0u;  // fetch counter of the next trace pass
@@ -2069,8 +2157,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
       if (j < nblk) {
         if (CAM) {
           const unsigned int q = (base + j) / nfr;
-          lsort[j] = once ? (int)((unsigned)S.active[0][q] * nfr + (base + j - q * nfr)) : (int)(base + j);
+          lsort[j] = once ? (int)((unsigned)S.hit[q] * nfr + (base + j - q * nfr)) : (int)(base + j);
           lpos[j] = (unsigned char)(q - base / nfr);
+        } else if (LEANR) {
+          const unsigned int q = (base + j) / nfr;
+          lsort[j] = (int)((unsigned)S.hit[q] * nfr + (base + j - q * nfr));
         } else {
           lsort[j] = W.cam_n ? (int)(base + j) : S.active[in][base + j];
         }
@@ -2078,7 +2169,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     }
     if (camrec) {  // the block-iteration's pixels' camera hits, one lane each (record = list position - p0)
       const unsigned int p0 = base / nfr, np = (base + nblk - 1u) / nfr - p0 + 1u;
-      if (threadIdx.x < np) cam_rec(W, E, once ? (unsigned)S.active[0][p0 + threadIdx.x] : p0 + threadIdx.x, lrec + kCamRec * threadIdx.x);
+      if (threadIdx.x < np) cam_rec(W, E, once ? (unsigned)S.hit[p0 + threadIdx.x] : p0 + threadIdx.x, lrec + kCamRec * threadIdx.x);
     }
   } else {
   int skey[SH_SUB], srank[SH_SUB], spath[SH_SUB];
@@ -2087,8 +2178,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     const unsigned int j = (unsigned)sub * 256u + threadIdx.x;
     skey[sub] = 0; srank[sub] = 0; spath[sub] = 0;
     if (j < nblk) {
-      spath[sub] = S.active[in][base + j];
-      skey[sub] = shade_key(P, S, spath[sub]);
+      if (LEANR) {
+        const unsigned int q = (base + j) / nfr;
+        spath[sub] = (int)((unsigned)S.hit[q] * nfr + (base + j - q * nfr));
+      } else {
+        spath[sub] = S.active[in][base + j];
+      }
+      skey[sub] = shade_key<LEANR>(P, S, spath[sub]);
       srank[sub] = (int)atomicAdd(&lhist[skey[sub]], 1u);
     }
   }
@@ -2110,8 +2206,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     // (an idle lane reads the position of an earlier block-iteration or none: a record inside lrec
     // or not, never read, as shade_path reads rec only for live paths)
     const float4* rec = camrec ? lrec + kCamRec * lpos[jj] : nullptr;
-    const ShadeOut so = shade_path<BSDF, FUSE, CAM>(W, E, path, live, CAM || W.cam_n != 0, !CAM && W.pass != 0, nsamples, rec);
+    const ShadeOut so = shade_path<BSDF, FUSE, CAM, LEAN>(W, E, path, live, CAM || W.cam_n != 0, !CAM && W.pass != 0, nsamples, rec);
     const bool qShadow = so.qShadow, qCont = so.qCont, keep = qShadow || qCont;
+    if (LEANW) {  // the shadow queue's entries; of the continuations and the kept paths only the counts
+      const unsigned int qs = wave_lds_append(&lc[0], qShadow ? 1u : 0u);
+      if (qShadow) lq[qs] = (path << 1) | 1;
+      const unsigned int nc = (unsigned int)__popcll(__ballot(qCont)), nk = (unsigned int)__popcll(__ballot(keep));
+      if ((threadIdx.x & 63u) == 0u) {
+        if (nc) atomicAdd(&lc[4], nc);
+        if (nk) atomicAdd(&lc[1], nk);
+      }
+      continue;
+    }
     // shadow rays from the front of the block's staging list, continuations from the back: the
     // block's queue run is [shadow rays][continuations], so a trace wave's claim is mostly one
     // kind
@@ -2123,6 +2229,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     if (keep) la[ai] = path;
   }
   __syncthreads();
+  if (LEANW) {  // (split_out holds: the host sets p1_lean only then)
+    if (threadIdx.x == 0) {
+      lc[2] = lc[0] ? atomicAdd(&S.cnt[cqs(out)], lc[0]) : 0u;
+      if (lc[4]) atomicAdd(&S.cnt[cq(out)], lc[4]);
+      if (lc[1]) atomicAdd(&S.cnt[ca(out)], lc[1]);
+    }
+    __syncthreads();
+    for (unsigned int j = threadIdx.x; j < lc[0]; j += 256u) S.queue_s[out][lc[2] + j] = lq[j];
+    __syncthreads();
+    continue;
+  }
   if (threadIdx.x == 0) {
     if (W.split_out) {  // shadow rays and continuations to their own queues
       lc[2] = lc[0] ? atomicAdd(&S.cnt[cqs(out)], lc[0]) : 0u;
