@@ -146,3 +146,17 @@ int dev_pass_report(rt_ctx* c, hipStream_t st, const rtd::WFParams& WP, int g, i
           us(ends[ends.size() * 99 / 100] - t0min), us(dmax), itmax, rmax);
   return RT_OK;
 }
+
+// development aid: after pass 1's shade, whether the group moved to the row arena
+// (WFParams::row_compact): pass 1's continuation hits as wf_p1_count counted them (4294967295: its
+// sample of a long list put them far above the capacity and the list was not counted), the rows the
+// arena holds for the group, the rows pass 1's shade claimed, and the decision of rtd::rows_on (syncs!)
+int dev_rows_report(rt_ctx* c, hipStream_t st, const rtd::WFParams& WP) {
+  unsigned int q[rtd::kCntRows + 1];
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipMemcpy(q, WP.S.cnt, sizeof(q), hipMemcpyDeviceToHost));
+  const unsigned int hits = q[rtd::kCntP1Hits], claimed = q[rtd::kCntRows];
+  fprintf(stderr, "[rt]   rows: enabled %d hits %u cap %u claimed %u compact %d\n", WP.row_compact, hits, WP.row_cap,
+          claimed, (RT_ROW_COMPACT && WP.row_compact && hits <= WP.row_cap) ? 1 : 0);
+  return RT_OK;
+}

@@ -143,6 +143,8 @@ struct rt_ctx {
                     // WFParams::p1_lean)
 #define RT_P1_LEAN 1
 #endif
+// RT_ROW_COMPACT (rt_wavefront.h): lean groups keep the state of passes >= 2 in dense rows
+// (WFParams::row_compact)
 #ifndef RT_CAM_SHARED_STATIC  // a bulk group's shared camera trace (one ray per work item: a small pass) runs the
                               // bulk's instantiation (0) or the small passes' (1: static shares, lane quads, every
                               // claim 64 rays): C3, 2.07 M rays of one 256-frame group standalone 0.299 vs 0.662 ms
@@ -179,6 +181,8 @@ struct rt_ctx {
   // costliest blocks and form pixel group 0 of a one-frame call; 0 = even split
   size_t order_head = 0;
   rtd::WFState wfg[MAX_GROUPS]{};
+  rtd::WFState wfa[MAX_GROUPS]{};             // each set's row arena (WFParams::A): wf_rows rows
+  size_t wf_rows = 0;
   hipStream_t aux[MAX_GROUPS] = {};
   unsigned int* d_pix = nullptr;   // pixel list of this rank: xy then accumulation index
   // tile ownership: owner[t] = rank of global tile t (default t % world; rt_set_tile_owners);
@@ -589,8 +593,19 @@ void update_frames_cap(rt_ctx* c, size_t nv) {
   c->frames_cap = (int)std::max<size_t>(1, std::min<size_t>(RT_MAX_FRAMES_PER_LAUNCH, max_slots / std::max<size_t>(1, nv)));
 }
 
+// Rows of a set's row arena (WFParams::A) and of a group's share of it.  A row is 148 B: s0-s4
+// (80), s5 (8), ra + rb and sa + sb (48), res (8) and rpath (4).  A quarter of the slots (C3 keeps
+// about 11 % of them after pass 1, C4's glass view nearly half: that one falls back) is 37 B per
+// slot, which fits the 40 B per slot of the four slot arrays a lean group neither reads nor writes
+// from pass 1 on (s1: every kept path is PF_ZLO; s5, rb, sb: pass 1 has no s5 row and 16-B rays), and
+// once a group runs on the arena it touches no slot array but fin.  So the arena is carved from
+// those arrays: the path state stays at 184 B per slot and the frames per launch where they were.
+// (whole groups of 4 rows: every arena array starts 16-B aligned)
+size_t arena_rows(size_t slots) { return slots / 4 & ~size_t(3); }
+
 // Path-state buffers of the wavefront path: `paths` slots for each of the n_groups frame
-// groups, carved from one allocation (184 B per slot + counters).  RT_ERR_NOMEM when HBM
+// groups, carved from one allocation (184 B per slot + counters; the row arena aliases four of the
+// slot arrays, arena_rows).  RT_ERR_NOMEM when HBM
 // cannot hold them (the caller then runs fewer frames at a time).
 static_assert(rt_ctx::MAX_GROUPS <= 4, "rtd::GroupCounters holds 4 groups' counters");
 int alloc_wavefront(rt_ctx* c, size_t paths) {
@@ -627,7 +642,21 @@ int alloc_wavefront(rt_ctx* c, size_t paths) {
     w.active[0] = (int*)carve(P * 4); w.active[1] = (int*)carve(P * 4);
     w.hit = (int*)carve(hit_cap * 4);
     w.cnt = (unsigned int*)carve(rtd::kCntWords * 4);
+    // the row arena: s0-s3 in s1's 16 P bytes, s4 and ra in s5's 8 P, sa, s5 and rb in rb's 8 P,
+    // sb, res and rpath in sb's 8 P (R <= P / 4 rows); everything else as the slot-indexed state
+    const size_t R = arena_rows(P);
+    rtd::WFState& a = c->wfa[g];
+    a = w;
+    char* q = (char*)w.s1;
+    a.s0 = (float4*)q; a.s1 = (float4*)(q + 16 * R); a.s2 = (float4*)(q + 32 * R); a.s3 = (float4*)(q + 48 * R);
+    q = (char*)w.s5;
+    a.s4 = (float4*)q; a.ra = (float4*)(q + 16 * R);
+    q = (char*)w.rb;
+    a.sa = (float4*)q; a.s5 = (decltype(a.s5))(q + 16 * R); a.rb = (float2*)(q + 24 * R);
+    q = (char*)w.sb;
+    a.sb = (float2*)q; a.res = (int*)(q + 8 * R); a.rpath = (unsigned int*)(q + 16 * R);
   }
+  c->wf_rows = arena_rows(P);
   c->wf_paths = P;
   c->wf_hit_cap = hit_cap;
   return RT_OK;
@@ -1328,6 +1357,13 @@ int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, co
     WP.cam_shared = 0;
     WP.cam_miss_once = 0;
     WP.p1_lean = 0;
+    WP.A = c->wfa[set];  // (the arena's own arrays; the per-call tables as S)
+    WP.A.pix_xy = WP.S.pix_xy;
+    WP.A.pix_acc = WP.S.pix_acc;
+    WP.A.cam = WP.S.cam;
+    WP.A.org = WP.S.org;
+    WP.row_compact = 0;
+    WP.row_cap = 0u;
     // (not for frame groups of one frame each: their blends must run in frame order)
     WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
     plan.slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
@@ -1438,6 +1474,15 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
       bool lean = RT_P1_LEAN && miss_once && WP.p1_compact && last_pass >= 1 && WP.split_out && !c->mats_emissive;
       if (const char* e = knob("RT_P1_LEAN")) lean = lean && atoi(e) != 0;  // (A/B)
       WP.p1_lean = lean ? 1 : 0;
+      // lean groups move the state of passes >= 2 to the row arena when pass 1's continuation hits
+      // fit a quarter of the group's slots (decided on the device: rtd::rows_on)
+      // (not when wf_finish ends the group's paths: it reads the slot-indexed state)
+      bool rowc = RT_ROW_COMPACT && lean && !finish;
+      if (const char* e = knob("RT_ROW_COMPACT")) rowc = rowc && atoi(e) != 0;  // (A/B)
+      size_t cap = std::min(arena_rows(slots), c->wf_rows);
+      if (const char* e = knob("RT_ROW_CAP")) cap = std::min(cap, (size_t)strtoull(e, nullptr, 10));  // (tests: rows)
+      WP.row_compact = rowc ? 1 : 0;
+      WP.row_cap = (unsigned int)cap;
       if (miss_once) {
         // (two blocks per CU: few waves, so few atomics on the list's counter)
         hipLaunchKernelGGL(rtd::wf_cam_classify, dim3(std::max(1u, std::min<unsigned int>(2u * (unsigned)c->n_cus, (WP.K.n_work + 255u) / 256u))),
@@ -1446,10 +1491,21 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
       }
     }
     const bool lean0 = WP.p1_lean && pass == 0, lean1 = WP.p1_lean && pass == 1;
+    if (lean1 && WP.row_compact) {  // the hits the shade will number with rows (rtd::rows_on reads the count)
+      const unsigned int items = (unsigned)std::min<size_t>(slots, (size_t)WP.K.n_work * (size_t)WP.n_frames);
+      const unsigned int runs = (items + 255u) / 256u;
+      hipLaunchKernelGGL(rtd::wf_p1_count<true>, dim3(std::max(1u, std::min<unsigned int>(8u * (unsigned)c->n_cus, runs / rtd::kP1SampleEvery + 1u))),
+                         dim3(256), 0, st, WP);
+      hipLaunchKernelGGL(rtd::wf_p1_count<false>, dim3(std::max(1u, std::min<unsigned int>(8u * (unsigned)c->n_cus, runs))), dim3(256), 0, st, WP);
+      HIPCHK(c, hipGetLastError());
+    }
     launch_shade(bsdf, WP.fuse_blend ? ShadeKind::fused : lean0 ? ShadeKind::cam_lean : cam ? ShadeKind::cam
                        : lean1 ? ShadeKind::bulk_lean : bulk ? ShadeKind::bulk : ShadeKind::plain,
                  slots, st, WP);
     HIPCHK(c, hipGetLastError());
+#ifdef RT_DEV
+    if (dev_passes() && pass == 1) if (int rc = dev_rows_report(c, st, WP)) return rc;
+#endif
   }
   return RT_OK;
 }

@@ -18,6 +18,10 @@
 //              list; pass 0's shade then runs over the hit pixels' frames only and wf_blend takes a
 //              miss pixel's samples from that record (WFParams::cam_miss_once)
 //
+//   wf_p1_count  (lean bulk groups, between pass 1's traces and its shade) the paths that can survive
+//              pass 1, against the rows of the dense arena that passes >= 2 then run on
+//              (WFParams::row_compact)
+//
 // wf_trace + wf_shade repeat maxBounce+1 times; passes with no work exit at once.  All frames
 // of one launch are in flight together (path slot = pixel * n_frames + frame): a pixel's frames
 // are independent until the progressive blend, so wf_blend applies RT:1552 afterwards in frame
@@ -83,6 +87,8 @@ struct WFState {
   // pass's shade writes active[0]
   int* __restrict__ hit;
   unsigned int* __restrict__ cnt;  // queue counts, active counts, trace fetch, segment claims (cq, ca, ... below)
+  // the row arena alone (WFParams::A; null in the slot-indexed state): the path slot of each row
+  unsigned int* __restrict__ rpath;
 };
 
 constexpr int kFlagNoRayHist = 1 << 30;  // (internal, development builds) KParams::flags: no per-ray histogram
@@ -100,6 +106,10 @@ constexpr unsigned int kCntFetch = 4u;
 // and, with WFParams::p1_lean, pass 1's continuation trace and shade read): a line of its own among
 // the unused words, zeroed with the others by wf_camera
 constexpr unsigned int kCntHit = 32u;
+// row arena (WFParams::row_compact), a line each among the unused words, zeroed by wf_camera too:
+// the continuation hits of pass 1 (wf_p1_count, after pass 1's traces: the rows its shade will claim),
+// and the rows claimed so far (one atomic per block-iteration of that shade)
+constexpr unsigned int kCntP1Hits = 64u, kCntRows = 96u;
 __host__ __device__ constexpr unsigned int xcnt(unsigned int s) { return 160u + 32u * s; }
 // split queues (WFParams::split): the shadow-ray queue counts of the two parities, and the claim
 // counters of its 8 segments (the continuation queue keeps cq / xcnt)
@@ -194,7 +204,31 @@ struct WFParams {
   // sixth of the paths have no shadow ray), and cnt[cq] / cnt[ca] still receive the continuation
   // and kept-path counts, so every statistic keeps its value
   int p1_lean;
+  // dense rows for the state of passes >= 2 (lean groups; RT_ROW_COMPACT).  About a tenth of a
+  // group's slots are alive after pass 1 and under 2 % by pass 5, so a slot-indexed 16-B or 8-B row
+  // of a late pass sits alone in its cache line.  Pass 1's shade (the LEAN reader) numbers its
+  // surviving paths -- key 1 of its block-local sort, the continuation hits -- with rows claimed from
+  // cnt[kCntRows] and writes their outgoing state, both rays and rpath[row] = slot to row `row` of
+  // the arena A; queue and active entries then hold rows, and passes >= 2 run on A in place (the
+  // slot is reloaded from rpath for the frame index and the fin store; fin stays slot-indexed).
+  // The arena holds row_cap rows, not the worst case, so every kernel from pass 1's shade on takes
+  // the same decision at its top (rows_on): cnt[kCntP1Hits], counted by wf_p1_count between pass
+  // 1's traces and its shade (or set beyond any capacity when a sample of the list shows the hits
+  // far above it), against row_cap.  Above it the group runs on the slot arrays as without this.  (Counting in pass 1's LEAN continuation trace instead -- a wave-uniform popcount
+  // kept in a scalar, or in an LDS word of the wave -- cost that instantiation 8 B of scratch and a
+  // VGPR spill at its 64 VGPRs, so the count is a kernel of its own: one launch per group.)
+  // A aliases the slot arrays a lean group does not read from pass 1 on (alloc_wavefront)
+  WFState A;
+  int row_compact;       // the group may run on the arena (set in pass 0 with p1_lean)
+  unsigned int row_cap;  // rows the arena holds for this group
 };
+#ifndef RT_ROW_COMPACT
+#define RT_ROW_COMPACT 1
+#endif
+// the group's passes >= 2 run on the row arena (uniform; valid from pass 1's shade on)
+RTD bool rows_on(const WFParams& W) { return RT_ROW_COMPACT && W.row_compact && W.S.cnt[kCntP1Hits] <= W.row_cap; }
+// the path slot of state index `path` of S: itself, or in the arena the row's slot
+RTD unsigned int slot_of(const WFState& S, int path) { return S.rpath ? S.rpath[path] : (unsigned int)path; }
 
 // Map a work index of this rank to (pixel, accumulation index); false outside the frame.
 RTD bool work_pixel(const KParams& P, unsigned int w, int& px, int& py, int& accIdx) {
@@ -1190,7 +1224,9 @@ void wf_trace(const WFParams W) {
   static_assert(!LEAN || (P1 && KIND == 1 && !CAM && !COUNT), "the lean protocol's continuation trace");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const KParams& P = W.K;
-  const WFState& S = W.S;
+  // passes >= 2 of a group on the row arena (WFParams::row_compact): queue entries are rows, and the
+  // rays and results are the arena's
+  const WFState& S = (!CAM && !P1 && W.pass >= 2 && rows_on(W)) ? W.A : W.S;
   const int qin = W.pass & 1;
   constexpr bool AHK = KIND == 2;  // every ray of the launch is any-hit
   const bool shared = CAM && W.cam_shared;  // one camera ray per work item: entry i = slot i * n_frames
@@ -1428,6 +1464,8 @@ void wf_trace(const WFParams W) {
       if (needPop) L.haveCur = tl_pop(P, L, TS, cull);
       if (!finished && !L.haveCur && L.tri_i >= L.tri_end) finished = true;
     }
+    // (LEAN) the continuation hits of pass 1, the rows its shade will claim (cnt[kCntP1Hits]):
+    // wave-uniform, outside the divergent branch below so that it stays a scalar
     if (busy && finished) {
       if (RT_RES_NT) __builtin_nontemporal_store(L.besttri, &S.res[entry]);
       else S.res[entry] = L.besttri;
@@ -1523,6 +1561,43 @@ RTD int shade_key(const KParams& P, const WFState& S, int path) {
   if (!(flags & PF_CONT) || t < 0) return 0;
   return 1;
 }
+// Pass 1's continuation hits of a lean group that may move to the row arena (WFParams::row_compact),
+// into cnt[kCntP1Hits]: the items pass 1's shade will give key 1, counted over the same list with
+// shade_key's test, one atomic per wave.  A path's continuation result is read first and its s2 row
+// (the flag byte) only when that result is a triangle: a path without a continuation has a stale
+// result, and one with a continuation always a fresh one.
+// Two launches per group.  SAMPLE: every kP1SampleEvery-th run of 256 items, into cnt[kCntP1Hits + 1].
+// Then the full count, unless the sample already puts the hits beyond one and a half times the
+// capacity: then the count is set to the largest value (the group stays on the slot arrays, which
+// is always right) and the list is not read again -- a scene whose paths mostly survive pass 1 pays
+// a sixteenth of the count.
+// Lists under kP1SampleMin items are counted in full whatever a sample would say: a few runs of a
+// small image's pixels estimate nothing, and their count costs nothing.
+constexpr unsigned int kP1SampleEvery = 16u, kP1SampleMin = 1u << 22;
+template <bool SAMPLE>
+__global__ __launch_bounds__(256) void wf_p1_count(const WFParams W) {
+  const WFState& S = W.S;
+  const unsigned int nfr = (unsigned int)W.n_frames, n_items = S.cnt[kCntHit] * nfr;
+  if (n_items < kP1SampleMin) {  // (uniform) a short list: the full count alone
+    if (SAMPLE) return;
+  } else if (!SAMPLE && (unsigned long long)S.cnt[kCntP1Hits + 1u] * kP1SampleEvery > (unsigned long long)W.row_cap + W.row_cap / 2u) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) S.cnt[kCntP1Hits] = 0xFFFFFFFFu;
+    return;
+  }
+  const unsigned int step = SAMPLE ? kP1SampleEvery : 1u;
+  unsigned int n = 0;  // (wave-uniform)
+  for (unsigned int b = blockIdx.x * step * 256u; b < n_items; b += gridDim.x * step * 256u) {
+    const unsigned int j = b + threadIdx.x;
+    bool hit = false;
+    if (j < n_items) {
+      const unsigned int q = j / nfr;
+      const unsigned int path = (unsigned)S.hit[q] * nfr + (j - q * nfr);
+      hit = S.res[2u * path] >= 0 && (__float_as_uint(S.s2[path].w) & PF_CONT) != 0u;
+    }
+    n += (unsigned int)__popcll(__ballot(hit));
+  }
+  if ((threadIdx.x & 63u) == 0u && n) atomicAdd(&S.cnt[kCntP1Hits + (SAMPLE ? 1u : 0u)], n);
+}
 #ifndef RT_SHADE_WPE  // 4 waves/SIMD (<= 128 VGPRs, 12 B/lane spill): shade -8% vs the natural 3
 #define RT_SHADE_WPE 4
 #endif
@@ -1536,6 +1611,9 @@ constexpr int SH_SUB = RT_SH_SUB, SH_SUB_BULK = RT_SH_SUB_BULK, SH_SUB_CAM = RT_
 // of the current bounce, sample the next one, write the state back and return the rays to queue.
 // camPass: the implicit camera pass (state built from the slot); loadPrev: the path has state
 // from an earlier pass (every pass but 0).
+// S, path: the state the step reads (and the fin row, by slot); SO, opath: where it writes the
+// outgoing state and rays -- the same, except in pass 1 of a group that moves to the row arena
+// (WFParams::row_compact), where S is the slot-indexed state and SO, opath the arena and the row.
 struct ShadeOut {
   bool qShadow, qCont;
 };
@@ -1705,11 +1783,11 @@ RTD uint32_t lean_seed(uint32_t cseed) {
 // CAMK: the camera pass of wf_shade<..., CAM> (every path's hit from its pixel's record)
 // LEAN (WFParams::p1_lean): with CAMK the writer of the lean pass-0 -> pass-1 state, else its reader
 // (pass 1 of such a group); both in instantiations of their own
-template <bool BSDF, bool FUSE = false, bool CAMK = false, bool LEAN = false>  // FUSE: W.fuse_blend is honoured (one-frame pixel groups)
-RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bool camPass, bool loadPrev,
-                        unsigned long long& nsamples, const float4* rec = nullptr) {
+// ROWS: S may be the row arena (the bulk's launches: wf_shade's ROWS); the others index by slot alone
+template <bool BSDF, bool FUSE = false, bool CAMK = false, bool LEAN = false, bool ROWS = false>  // FUSE: W.fuse_blend is honoured (one-frame pixel groups)
+RTD ShadeOut shade_path(const WFParams& W, const WFState& S, const WFState& SO, const Env& E, int path, int opath,
+                        bool live, bool camPass, bool loadPrev, unsigned long long& nsamples, const float4* rec = nullptr) {
   const KParams& P = W.K;
-  const WFState& S = W.S;
   bool doFinish = false, doBounce = false;
   bool qShadow = false, qCont = false;
   f3 fin = splat(0.0f);
@@ -1736,7 +1814,7 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
     } else {
       const uint2 p5 = S.s5[path];
       const unsigned int nfr = (unsigned int)W.n_frames;
-      a5 = make_uint4(p5.x, p5.y >> 8, p5.y & 0xffu, (unsigned int)path % nfr);
+      a5 = make_uint4(p5.x, p5.y >> 8, p5.y & 0xffu, (ROWS ? slot_of(S, path) : (unsigned int)path) % nfr);
     }
     // every load of the path's state issues at once: camera paths exist only in pass 0 (a
     // uniform test), so no load waits for the flags; the flags still decide what is used
@@ -2039,7 +2117,8 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
       const f3 acc = bw.x * fin + bw.y * mk3(h.x, h.y, h.z);
       P.accum[ai] = make_float4(acc.x, acc.y, acc.z, 0.0f);
     } else {
-      st_row(S.fin + path, make_float4(fin.x, fin.y, fin.z, 0.0f));
+      // (ROWS: the arena's slot reloaded here, not held across the bounce)
+      st_row(S.fin + (ROWS ? slot_of(S, path) : (unsigned int)path), make_float4(fin.x, fin.y, fin.z, 0.0f));
     }
     nsamples++;
   }
@@ -2050,33 +2129,34 @@ RTD ShadeOut shade_path(const WFParams& W, const Env& E, int path, bool live, bo
     if (live) {
       // (Lo and Le0 are +0 here: Lo starts the path, and no material of the scene is emissive)
       if (keep) nflags |= PF_ZLO;
-      if (keep) st_row(S.s0 + path, make_float4(hist.x, hist.y, hist.z, evp));
-      st_row(S.s2 + path, make_float4(evf.x, evf.y, evf.z, __uint_as_float(keep ? nflags : 0u)));
-      if (qShadow) st_row(S.s3 + path, make_float4(cnee.x, cnee.y, cnee.z, 0.0f));
-      if (nflags & PF_CMED) st_row(S.s4 + path, make_float4(cmed.x, cmed.y, cmed.z, 0.0f));
-      if (!BSDF && qCont) st_row(S.s4 + path, make_float4(bNdotL, 0.0f, 0.0f, 0.0f));
+      if (keep) st_row(SO.s0 + opath, make_float4(hist.x, hist.y, hist.z, evp));
+      st_row(SO.s2 + opath, make_float4(evf.x, evf.y, evf.z, __uint_as_float(keep ? nflags : 0u)));
+      if (qShadow) st_row(SO.s3 + opath, make_float4(cnee.x, cnee.y, cnee.z, 0.0f));
+      if (nflags & PF_CMED) st_row(SO.s4 + opath, make_float4(cmed.x, cmed.y, cmed.z, 0.0f));
+      if (!BSDF && qCont) st_row(SO.s4 + opath, make_float4(bNdotL, 0.0f, 0.0f, 0.0f));
       // every listed path has an ra row: zeros without a continuation (never a ray: a sampled
       // direction has unit length), which pass 1's continuation trace skips
-      if (qCont || P.max_bounce > 0) st_row(S.ra + path, qCont ? make_float4(contD.x, contD.y, contD.z, contS) : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-      if (qShadow) st_row(S.sa + path, make_float4(shD.x, shD.y, shD.z, 0.0f));
+      if (qCont || P.max_bounce > 0) st_row(SO.ra + opath, qCont ? make_float4(contD.x, contD.y, contD.z, contS) : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+      if (qShadow) st_row(SO.sa + opath, make_float4(shD.x, shD.y, shD.z, 0.0f));
     }
   } else if (keep) {
     const bool zlo = (__float_as_uint(Lo.x) | __float_as_uint(Lo.y) | __float_as_uint(Lo.z) |
                                 __float_as_uint(Le0.x) | __float_as_uint(Le0.y) | __float_as_uint(Le0.z)) == 0u;
     if (zlo) nflags |= PF_ZLO;
-    st_row(S.s0 + path, make_float4(hist.x, hist.y, hist.z, evp));
-    if (!zlo) st_row(S.s1 + path, make_float4(Lo.x, Lo.y, Lo.z, Le0.x));
-    st_row(S.s2 + path, make_float4(evf.x, evf.y, evf.z, Le0.y));
-    if (!zlo || qShadow) st_row(S.s3 + path, make_float4(cnee.x, cnee.y, cnee.z, Le0.z));
-    if (nflags & PF_CMED) st_row(S.s4 + path, make_float4(cmed.x, cmed.y, cmed.z, 0.0f));
-    if (!BSDF && qCont) st_row(S.s4 + path, make_float4(bNdotL, 0.0f, 0.0f, 0.0f));
-    st_row(S.s5 + path, make_uint2(wseed, bounce << 8 | nflags));
+    st_row(SO.s0 + opath, make_float4(hist.x, hist.y, hist.z, evp));
+    if (!zlo) st_row(SO.s1 + opath, make_float4(Lo.x, Lo.y, Lo.z, Le0.x));
+    st_row(SO.s2 + opath, make_float4(evf.x, evf.y, evf.z, Le0.y));
+    if (!zlo || qShadow) st_row(SO.s3 + opath, make_float4(cnee.x, cnee.y, cnee.z, Le0.z));
+    if (nflags & PF_CMED) st_row(SO.s4 + opath, make_float4(cmed.x, cmed.y, cmed.z, 0.0f));
+    if (!BSDF && qCont) st_row(SO.s4 + opath, make_float4(bNdotL, 0.0f, 0.0f, 0.0f));
+    st_row(SO.s5 + opath, make_uint2(wseed, bounce << 8 | nflags));
+    if (ROWS && LEAN && !CAMK && SO.rpath) SO.rpath[opath] = (unsigned int)path;  // pass 1 fills the arena: the row's slot
     if (camPass && W.p1_compact) {  // (uniform) 16-B rays from the pixel's camera hit point
-      if (qCont) st_row(S.ra + path, make_float4(contD.x, contD.y, contD.z, contS));
-      if (qShadow) st_row(S.sa + path, make_float4(shD.x, shD.y, shD.z, 0.0f));
+      if (qCont) st_row(SO.ra + opath, make_float4(contD.x, contD.y, contD.z, contS));
+      if (qShadow) st_row(SO.sa + opath, make_float4(shD.x, shD.y, shD.z, 0.0f));
     } else {
-      if (qCont) put_ray(S.ra, S.rb, path, contO.x, contO.y, contO.z, contD.x, contD.y, contD.z);
-      if (qShadow) put_ray(S.sa, S.sb, path, shO.x, shO.y, shO.z, shD.x, shD.y, shD.z);
+      if (qCont) put_ray(SO.ra, SO.rb, opath, contO.x, contO.y, contO.z, contD.x, contD.y, contD.z);
+      if (qShadow) put_ray(SO.sa, SO.sb, opath, shO.x, shO.y, shO.z, shD.x, shD.y, shD.z);
     }
   }
   return ShadeOut{qShadow, qCont};
@@ -2098,6 +2178,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   __shared__ int lsort[256 * SH_SUB];  // the block's paths, grouped by shade_key
   __shared__ unsigned int lhist[SH_KEYS], lofs[SH_KEYS];
   __shared__ unsigned int lc[6];  // queue count (shadow rays), active count, queue base, active base, continuations, (split) their base
+  __shared__ unsigned int lrow;   // (LEANR on its way to the row arena) the first row of the block-iteration's claim
   constexpr unsigned int kRecs = 256u * SH_SUB / 64u + 1u;  // pixels a block-iteration spans at >= 64 frames
   __shared__ float4 lrec[CAM ? kCamRec * kRecs : 1];
   // CAM: the record of each staged path (its pixel's position among the block-iteration's pixels),
@@ -2106,10 +2187,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   // 4 waves/SIMD = 4 blocks per CU: the block's LDS must fit a quarter of the CU's 160 KB
   static_assert(kRecs <= 256u, "lpos holds a byte per path");
   static_assert(4 * (2 * 256 * SH_SUB + 2 * 256 * SH_SUB) + 16 * (CAM ? kCamRec * kRecs : 1) + (CAM ? 256 * SH_SUB : 1) +
-                    8 * SH_KEYS + 24 <= 40960,
+                    8 * SH_KEYS + 24 + 4 <= 40960,
                 "wf_shade LDS exceeds a quarter of the CU");
   const KParams& P = W.K;
-  const WFState& S = W.S;
+  // the row arena (WFParams::row_compact; the bulk's launches alone): pass 1 of a lean group reads
+  // the slot-indexed state S and writes the survivors' to rows of SO = W.A; the later passes run on
+  // W.A in place.  One uniform decision per launch, the same in every kernel of the group
+  constexpr bool ROWS = !CAM && !FUSE && SH_SUB == rtd::SH_SUB_BULK;
+  const bool rows_out = ROWS && (LEANR || W.pass >= 2) && rows_on(W), rows_in = rows_out && !LEANR;
+  const WFState& S = rows_in ? W.A : W.S;
+  const WFState& SO = rows_out ? W.A : W.S;
   const int in = W.pass & 1, out = in ^ 1;
   const unsigned int nfr = (unsigned int)W.n_frames;
   constexpr bool camrec = CAM;
@@ -2149,7 +2236,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   __syncthreads();
   // sort only passes holding at least a quarter of the group's path slots (in practice pass 1,
   // whatever the per-rank pixel share)
-  const bool sort_pass = !CAM && W.pass != 0 && na >= max(1u << 22, (unsigned)W.n_frames * P.n_work / 4u);
+  // (a pass 1 that fills the row arena sorts whatever its size: the sort numbers the rows)
+  const bool sort_pass = !CAM && W.pass != 0 && (na >= max(1u << 22, (unsigned)W.n_frames * P.n_work / 4u) || (LEANR && rows_out));
   if (!sort_pass) {  // camera pass: hit/miss divergence is low already
 #pragma unroll
     for (int sub = 0; sub < SH_SUB; sub++) {
@@ -2192,6 +2280,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
   if (threadIdx.x == 0) {
     unsigned int acc = 0;
     for (int k = 0; k < SH_KEYS; k++) { lofs[k] = acc; acc += lhist[k]; }
+    // the key-1 paths (a continuation hit: the only ones that can survive pass 1) take the next
+    // lhist[1] rows, in sorted order; one that queues nothing leaves a hole nothing lists.  All
+    // claims of the launch add up to cnt[kCntP1Hits] <= row_cap (rows_on)
+    if (LEANR && rows_out) lrow = lhist[1] ? atomicAdd(&S.cnt[kCntRows], lhist[1]) : 0u;
   }
   __syncthreads();
 #pragma unroll
@@ -2206,7 +2298,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     // (an idle lane reads the position of an earlier block-iteration or none: a record inside lrec
     // or not, never read, as shade_path reads rec only for live paths)
     const float4* rec = camrec ? lrec + kCamRec * lpos[jj] : nullptr;
-    const ShadeOut so = shade_path<BSDF, FUSE, CAM, LEAN>(W, E, path, live, CAM || W.cam_n != 0, !CAM && W.pass != 0, nsamples, rec);
+    int opath = path;  // where the path's outgoing state goes, and what the next pass's lists hold
+    if (LEANR && rows_out && live && jj >= lofs[1]) opath = (int)(lrow + (jj - lofs[1]));
+    const ShadeOut so = shade_path<BSDF, FUSE, CAM, LEAN, ROWS>(W, S, SO, E, path, opath, live, CAM || W.cam_n != 0, !CAM && W.pass != 0, nsamples, rec);
     const bool qShadow = so.qShadow, qCont = so.qCont, keep = qShadow || qCont;
     if (LEANW) {  // the shadow queue's entries; of the continuations and the kept paths only the counts
       const unsigned int qs = wave_lds_append(&lc[0], qShadow ? 1u : 0u);
@@ -2223,10 +2317,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SHADE_WP
     // kind
     const unsigned int qs = wave_lds_append(&lc[0], qShadow ? 1u : 0u);
     const unsigned int qc = wave_lds_append(&lc[4], qCont ? 1u : 0u);
-    if (qShadow) lq[qs] = (path << 1) | 1;
-    if (qCont) lq[2 * 256 * SH_SUB - 1 - qc] = path << 1;
+    if (qShadow) lq[qs] = (opath << 1) | 1;
+    if (qCont) lq[2 * 256 * SH_SUB - 1 - qc] = opath << 1;
     const unsigned int ai = wave_lds_append(&lc[1], keep ? 1u : 0u);
-    if (keep) la[ai] = path;
+    if (keep) la[ai] = opath;
   }
   __syncthreads();
   if (LEANW) {  // (split_out holds: the host sets p1_lean only then)
@@ -2457,7 +2551,7 @@ void wf_finish(const WFParams W) {
       const KParams& PL = Wl->K;
       const Env EL{PL.hdr, PL.cache, PL.light, PL.hdr_w, PL.hdr_h, PL.hdr_res, PL.env_angle, PL.env_intensity};
       unsigned long long ns = 0;  // (a coop group runs its path's shade step on all its lanes: counted once)
-      const ShadeOut o = shade_path<BSDF, true>(*Wl, EL, path, sh, false, true, ns);
+      const ShadeOut o = shade_path<BSDF, true>(*Wl, Wl->S, Wl->S, EL, path, path, sh, false, true, ns);
       if (lead()) nsamples += ns;
       if (sh) {
         if (lead()) nsteps++;
