@@ -56,8 +56,12 @@
  * 7: ray queries: rt_ray, rt_hit, RT_HIT_INVALID, RT_QUERY_*, rt_trace_rays, rt_trace_rays_device,
  *    rt_camera_rays, rt_first_hit, rt_first_hit_device, rt_pick, rt_get_triangle_material.  Additive:
  *    every ABI-6 entry point and struct is unchanged, and rendering computes what it did.
+ *    The display denoiser (RT_HAS_DENOISE: rt_denoise_params, RT_DENOISE_*, rt_denoise_default_params,
+ *    rt_denoise_async, rt_denoise) is an addition within ABI 7: nothing else changed, the version
+ *    stays 7, and a binding finds it by symbol (a library built before it lacks rt_denoise).
  * A binding checks rt_abi_version() at load time. */
 #define RT_ABI_VERSION 7
+#define RT_HAS_DENOISE 1
 
 #ifdef __cplusplus
 extern "C" {
@@ -354,6 +358,52 @@ int rt_pick(rt_ctx* ctx, const rt_frame_params* params, int32_t px, int32_t py, 
  * of the new material (a new one unless the table already holds it), so what a pick returns can
  * be edited and fed back to rt_update_materials(triangle, 1, ...).  Either output may be NULL. */
 int rt_get_triangle_material(rt_ctx* ctx, int32_t triangle, rt_material* out, int32_t* material_id);
+
+/* ---- Display denoiser (RT_HAS_DENOISE, within ABI 7; no counterpart in the reference, whose display
+ * pass main.cpp:202-228 shows the raw accumulation): a guided edge-avoiding a-trous wavelet filter
+ * (Dammertz et al. 2010) over the accumulation and the first-hit records, for a readable image after
+ * one or a few samples per pixel.  It is a post-process between rendering and rt_tonemap(_async): it
+ * leaves LoopNum, the accumulation, the path state, rt_order_work's order and every rt_stats field
+ * as they were.  All arithmetic is fp32 in a fixed order (tests/denoise_model.py is
+ * the same filter in numpy, and the two agree bit for bit).  Iteration i = 0 .. iterations-1 runs a
+ * 5x5 B3-spline footprint with taps s = 2^i apart; a tap counts when it lies in the frame, hit
+ * something, has the centre's material and a finite colour, weighted by
+ * exp(-(|dN|^2 / sigma_normal^2 + (N . dP / t)^2 / sigma_plane^2 + |dG|^2 * 4^i / sigma_color^2)), G the
+ * colour compressed by 1 / (1 + luminance).  Pixels whose camera ray misses pass through bit for
+ * bit (they show the environment, which carries no noise); a non-finite pixel is never a source and
+ * is filled from its neighbours by the geometric weights alone.
+ * Out of scope: multi-rank contexts (a rank has guides for its own pixels only: RT_ERR_STATE when
+ * world != 1), temporal reprojection, variance estimation, albedo demodulation. */
+typedef struct rt_denoise_params {
+  int32_t iterations;               /* 1..5 */
+  float sigma_color, sigma_normal, sigma_plane;   /* each finite and > 0 */
+  int32_t flags;                    /* RT_DENOISE_* */
+} rt_denoise_params;                /* 20 bytes */
+/* REUSE_GUIDES: use the guides (normal, position, depth, material per pixel) of this context's
+ * previous denoise call; the caller asserts that the camera, scene, materials and size are
+ * unchanged since.  fp and hits_dev are ignored. */
+enum { RT_DENOISE_REUSE_GUIDES = 1 };
+/* The defaults: 5 iterations, sigma_color 1.0, sigma_normal 0.3, sigma_plane 0.01, flags 0. */
+int rt_denoise_default_params(rt_denoise_params* dp);
+/* Enqueue the filter on the ctx stream, after the render calls queued before it (pipelined ones
+ * included); a render call queued afterwards blends only after the filter has read the
+ * accumulation.  frame_in_device: width*height*3 floats in RT_LAYOUT_FRAME order on the device, or
+ * NULL for this context's accumulation.  hits_dev: the first-hit frame as rt_first_hit_device
+ * writes it (the camera pass's hit record, RT:1519), or NULL: the library traces it for fp (only its
+ * camera fields and RT_FLAG_NO_CULL are read) into a buffer of its own.  *frame_out_device
+ * receives the context-owned output frame (width*height*3 floats, RT_LAYOUT_FRAME order), valid in
+ * stream order until the next denoise call, rt_resize or rt_destroy; it can be passed to
+ * rt_tonemap(_async) as frame_device.  The buffers (two colour frames, two guide frames, the rt_hit
+ * frame, the output: 76 B per pixel + 48 B per tile pixel) are the context's own, allocated on first
+ * use, dropped and re-sized by rt_resize, freed by rt_destroy.
+ * RT_ERR_ARG: a null pointer (fp may be NULL when it is ignored), iterations outside 1..5, a sigma
+ * that is not finite and > 0, unknown flags.  RT_ERR_STATE: before rt_set_scene or rt_resize; a
+ * context with world != 1; RT_DENOISE_REUSE_GUIDES when no guides exist for the current size. */
+int rt_denoise_async(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_params* dp,
+                     const float* frame_in_device, const void* hits_dev, float** frame_out_device);
+/* The same on this context's accumulation with the library's own first-hit trace (RT:1519),
+ * synchronous: rgb_out_host = width*height*3 floats, RT_LAYOUT_FRAME order (row 0 = bottom). */
+int rt_denoise(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_params* dp, float* rgb_out_host);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
 #include "rt_kernels.h"
 #include "rt_wavefront.h"
 #include "rt_query.h"
+#include "rt_denoise.h"
 
 #ifndef RT_SPLIT_KINDS  // bulk groups trace shadow rays and continuations in launches of their own (round 6)
 #define RT_SPLIT_KINDS 1
@@ -241,6 +242,17 @@ struct rt_ctx {
     int2* d_ovf = nullptr;       // the traversal's overflow stack of the query launches
     size_t ovf_bytes = 0;
   } q;
+  // The display denoiser (rt_denoise*; rt_denoise.h): frame-order buffers of W*H pixels, allocated
+  // on first use, dropped by a resize (the next call allocates the new size) and by rt_destroy
+  struct Denoise {
+    void* mem = nullptr;
+    float4* col[2] = {nullptr, nullptr};  // ping-pong colour {r, g, b, k}
+    float4* g0 = nullptr;                 // guides {N.xyz, bits(M or -1)}
+    float4* g1 = nullptr;                 //        {P.xyz, 1/t}
+    float4* hits = nullptr;               // the library's own first-hit frame (rt_hit, local-tile layout)
+    float* out = nullptr;                 // the output frame, W*H*3 floats
+    bool guides = false;                  // g0 / g1 hold a denoise call's guides for the current size
+  } dn;
 };
 
 namespace {
@@ -731,6 +743,7 @@ int rt_destroy(rt_ctx* c) {
   dfree(c->d_stack_ovf);
   if (c->q.mem) (void)hipFree(c->q.mem);
   dfree(c->q.d_ovf);
+  if (c->dn.mem) (void)hipFree(c->dn.mem);
   dfree(c->d_disp);
   dfree(c->d_gather);
   for (auto& m : c->rccl_comms) (void)ncclCommDestroy(m);
@@ -857,6 +870,8 @@ static int apply_tiling(rt_ctx* c, int width, int height, const rt_tiling& tl, s
   // the old pixel lists / accumulation no longer describe the frame from here on: a failure
   // below leaves the context un-sized (rt_render_async then refuses) rather than half-resized
   c->frame_set = false;
+  if (c->dn.mem) (void)hipFree(c->dn.mem);  // the denoiser's frames and guides are the old size's
+  c->dn = rt_ctx::Denoise{};
   c->W = width; c->H = height;
   c->tile_w = tl.tile_w; c->tile_h = tl.tile_h; c->rank = tl.rank; c->world = tl.world;
   c->tiles_x = (width + tl.tile_w - 1) / tl.tile_w;
@@ -2399,6 +2414,144 @@ int rt_get_triangle_material(rt_ctx* c, int32_t triangle, rt_material* out, int3
   const int id = c->tri_mat[(size_t)triangle];
   if (out) memcpy(out, &c->mat_table[32 * (size_t)id], sizeof(rt_material));  // pack_material keeps the 24 floats verbatim
   if (material_id) *material_id = id;
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------- display denoiser
+namespace {
+
+// An iteration with s >= 4 runs the LDS kernel over one residue class per block (true) or direct
+// global reads.  C3 1080p, us per launch, class / direct: s = 4 125 / 97, s = 8 83 / 104, s = 16
+// 84 / 99 (Appendix A has the form rejected at each step).  RT_DN_FAR=lds|direct
+// (development build) forces one form for every s >= 4, to repeat that measurement.
+bool dn_far_lds(int s) {
+  if (const char* e = knob("RT_DN_FAR")) return strcmp(e, "lds") == 0;
+  return s >= 8;
+}
+
+// The denoiser's buffers for the current frame size (apply_tiling dropped those of another size)
+int reserve_denoise(rt_ctx* c) {
+  rt_ctx::Denoise& d = c->dn;
+  if (d.mem) return RT_OK;
+  const size_t npx = (size_t)c->W * c->H;
+  const size_t hit_bytes = (size_t)std::max(1, c->local_tiles) * c->tile_w * c->tile_h * sizeof(rt_hit);
+  auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t bytes = 4 * pad(npx * 16) + pad(hit_bytes) + pad(npx * 12);
+  const hipError_t me = hipMalloc(&d.mem, bytes);
+  if (me == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    d.mem = nullptr;
+    return fail(c, RT_ERR_NOMEM, "denoise buffers do not fit in device memory");
+  }
+  HIPCHK(c, me);
+  char* p = static_cast<char*>(d.mem);
+  auto carve = [&](size_t b) { char* r = p; p += pad(b); return r; };
+  d.col[0] = (float4*)carve(npx * 16);
+  d.col[1] = (float4*)carve(npx * 16);
+  d.g0 = (float4*)carve(npx * 16);
+  d.g1 = (float4*)carve(npx * 16);
+  d.hits = (float4*)carve(hit_bytes);
+  d.out = (float*)carve(npx * 12);
+  d.guides = false;
+  return RT_OK;
+}
+
+bool dn_sigma_ok(float s) { return std::isfinite(s) && s > 0.0f; }
+
+}  // namespace
+
+extern "C" {
+
+int rt_denoise_default_params(rt_denoise_params* dp) {
+  if (!dp) return RT_ERR_ARG;
+  dp->iterations = 5;
+  dp->sigma_color = 1.0f;
+  dp->sigma_normal = 0.3f;
+  dp->sigma_plane = 0.01f;
+  dp->flags = 0;
+  return RT_OK;
+}
+
+int rt_denoise_async(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_params* dp, const float* frame_in_device,
+                     const void* hits_dev, float** frame_out_device) {
+  if (!c) return RT_ERR_ARG;
+  if (!dp || !frame_out_device) return fail(c, RT_ERR_ARG, "null parameters or output");
+  if (dp->iterations < 1 || dp->iterations > 5) return fail(c, RT_ERR_ARG, "iterations outside 1..5");
+  if (!dn_sigma_ok(dp->sigma_color) || !dn_sigma_ok(dp->sigma_normal) || !dn_sigma_ok(dp->sigma_plane))
+    return fail(c, RT_ERR_ARG, "a sigma is not finite and > 0");
+  if (dp->flags & ~RT_DENOISE_REUSE_GUIDES) return fail(c, RT_ERR_ARG, "unknown flags");
+  const bool reuse = (dp->flags & RT_DENOISE_REUSE_GUIDES) != 0;
+  const bool trace = !reuse && !hits_dev;
+  if (trace && !fp) return fail(c, RT_ERR_ARG, "null frame parameters");
+  if (!c->scene_set || !c->frame_set) return fail(c, RT_ERR_STATE, "rt_set_scene and rt_resize first");
+  if (c->world != 1) return fail(c, RT_ERR_STATE, "a multi-rank context has guides for its own pixels only");
+  if (reuse && !(c->dn.mem && c->dn.guides)) return fail(c, RT_ERR_STATE, "no guides of an earlier denoise call for this size");
+  if (trace)
+    if (int rc = camera_args(c, fp, true)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = reserve_denoise(c)) return rc;
+  rt_ctx::Denoise& d = c->dn;
+  if (trace) {
+    d.guides = false;  // (they are being replaced: a failure below leaves none)
+    if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
+  }
+  // The pack reads the accumulation on the ctx stream, after the render calls queued before it
+  // (the stream joins each of them); a render call queued afterwards blends only after it, as
+  // after rt_tonemap_async's pass (a pipelined call's blend waits for the ctx stream at its entry).
+  const dim3 pgrid((c->W + 255) / 256, c->H);
+  const float4* tiles = frame_in_device ? nullptr : c->d_accum;
+  if (reuse)
+    hipLaunchKernelGGL(rtd::dn_pack<false>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device, (const float4*)nullptr,
+                       d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w, c->tile_h, c->tiles_x);
+  else
+    hipLaunchKernelGGL(rtd::dn_pack<true>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device,
+                       hits_dev ? (const float4*)hits_dev : d.hits, d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w,
+                       c->tile_h, c->tiles_x);
+  HIPCHK(c, hipGetLastError());
+  d.guides = true;
+  rtd::DnIter I;
+  I.g0 = d.g0;
+  I.g1 = d.g1;
+  I.W = c->W;
+  I.H = c->H;
+  I.kn = 1.0f / (dp->sigma_normal * dp->sigma_normal);
+  I.kp = 1.0f / (dp->sigma_plane * dp->sigma_plane);
+  I.kc = 1.0f / (dp->sigma_color * dp->sigma_color);
+  for (int i = 0; i < dp->iterations; i++) {
+    const bool last = i + 1 == dp->iterations;
+    const int s = 1 << i;
+    I.cin = d.col[i & 1];
+    I.cout = last ? nullptr : d.col[(i + 1) & 1];
+    I.out3 = last ? d.out : nullptr;
+    I.s = s;
+    auto tiles_of = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
+    if (s <= 2) {
+      const dim3 grid(tiles_of(c->W, rtd::kDnTW), tiles_of(c->H, rtd::kDnTH), 1);
+      if (s == 1) hipLaunchKernelGGL(rtd::dn_atrous_lds<1>, grid, dim3(256), 0, c->stream, I, 1);
+      else hipLaunchKernelGGL(rtd::dn_atrous_lds<2>, grid, dim3(256), 0, c->stream, I, 1);
+    } else if (dn_far_lds(s)) {  // class (0, 0) is the largest: ceil(W / s) x ceil(H / s)
+      const dim3 grid(tiles_of((c->W + s - 1) / s, rtd::kDnTW), tiles_of((c->H + s - 1) / s, rtd::kDnTH), (unsigned)(s * s));
+      hipLaunchKernelGGL(rtd::dn_atrous_lds<1>, grid, dim3(256), 0, c->stream, I, s);
+    } else {
+      const dim3 grid(tiles_of(c->W, rtd::kDnTW), tiles_of(c->H, rtd::kDnTH), 1);
+      hipLaunchKernelGGL(rtd::dn_atrous_direct, grid, dim3(256), 0, c->stream, I);
+    }
+    HIPCHK(c, hipGetLastError());
+    I.kc = I.kc * 4.0f;
+  }
+  *frame_out_device = d.out;
+  return RT_OK;
+}
+
+int rt_denoise(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_params* dp, float* rgb_out_host) {
+  if (!c) return RT_ERR_ARG;
+  if (!rgb_out_host) return fail(c, RT_ERR_ARG, "null output");
+  float* out = nullptr;
+  if (int rc = rt_denoise_async(c, fp, dp, nullptr, nullptr, &out)) return rc;
+  HIPCHK(c, hipMemcpyAsync(rgb_out_host, out, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
 

@@ -115,10 +115,11 @@ class Settings:
     env_angle: float = 0.0
     max_bounce: int = 8
     max_iterations: int = 3000
+    enable_denoise: bool = False  # (no counterpart in the reference) rt_denoise before the display pass
 
 
 # OnGUI controls that restart the accumulation (main.cpp:343-368, :408); tone mapping / gamma
-# only change the display pass (main.cpp:373-374)
+# (main.cpp:373-374) and the denoiser only change the display pass
 RESETTING = {"enable_env_map", "env_intensity", "env_angle", "enable_mis", "max_bounce", "max_iterations",
              "enable_bsdf"}
 
@@ -169,6 +170,9 @@ class Session:
         self.first_mouse = True                               # RenderSettings.h:29-31
         self.last_x, self.last_y = f32(1024 / 2.0), f32(512 / 2.0)
         self.last_time: Optional[float] = None
+        # the denoiser's guides (first-hit frame) are those of this session's last denoise call and
+        # still describe the view: no r.reset() (camera, settings, materials) or resize since
+        self._guides_current = False
 
     # main.cpp:296-318
     def _mouse(self, xpos: float, ypos: float, rmb: bool) -> None:
@@ -200,6 +204,7 @@ class Session:
             self.width, self.height = inp.resize
             self.camera.process_screen_ratio(self.width, self.height)
             self.r.resize(self.width, self.height)
+            self._guides_current = False
         for x, y, rmb in inp.mouse:
             self._mouse(x, y, rmb)
         held = {k.upper() for k in inp.keys}
@@ -226,6 +231,7 @@ class Session:
             reset = True
         if self.camera.take_reset() or reset:
             self.r.reset()
+            self._guides_current = False
         fp = self.frame_params()
         picked = self._pick(fp, *inp.pick) if inp.pick is not None else None
         ro = self._rand[self.frame:self.frame + 1]
@@ -242,14 +248,20 @@ class Session:
         flags = (RT_DISPLAY_TONEMAP if s.enable_tone_mapping else 0) | \
                 (RT_DISPLAY_GAMMA if s.enable_tone_mapping and s.enable_gamma_correction else 0)
         out["display_flags"] = flags
+        # the displayed frame: the accumulation itself (frame_ptr omitted: today's calls), or its
+        # denoised copy on the device, queued behind the frame on the renderer's stream
+        shown = {}
+        if display and s.enable_denoise:
+            shown["frame_ptr"] = self.r.denoise_async(fp, reuse_guides=self._guides_current)
+            self._guides_current = True
         if self.in_flight == 1:
             if display:
-                out["image"] = self.r.tonemap(flags)
+                out["image"] = self.r.tonemap(flags, **shown)
             return out
         slot = None
         if display:
             slot = self.frame % 4  # at most 3 queued: a slot is fetched before it is reused
-            self.r.tonemap_async(slot, flags)
+            self.r.tonemap_async(slot, flags, **shown)
         self._queued.append((out, slot))
         return self._fetch_oldest() if len(self._queued) >= self.in_flight else None
 

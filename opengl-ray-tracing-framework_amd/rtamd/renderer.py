@@ -48,8 +48,11 @@ ABI_SYMBOLS = (
     "rt_gather_last_transport",
     "rt_trace_rays", "rt_trace_rays_device", "rt_camera_rays", "rt_first_hit", "rt_first_hit_device", "rt_pick",
     "rt_get_triangle_material",
+    "rt_denoise_default_params", "rt_denoise_async", "rt_denoise",
 )
 RT_DISPLAY_TONEMAP, RT_DISPLAY_GAMMA = 1, 2
+RT_HAS_DENOISE = 1
+RT_DENOISE_REUSE_GUIDES = 1
 
 
 class RtMaterial(C.Structure):
@@ -175,6 +178,26 @@ class FrameParams:
         return p
 
 
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float), ("flags", C.c_int32)]
+
+
+@dataclasses.dataclass
+class DenoiseParams:
+    """rt_denoise_params with rt_denoise_default_params' values: a-trous iterations (1..5, taps 2^i
+    apart) and the edge-stopping sigmas of colour, normal and plane distance."""
+    iterations: int = 5
+    sigma_color: float = 1.0
+    sigma_normal: float = 0.3
+    sigma_plane: float = 0.01
+    flags: int = 0
+
+    def to_c(self, extra_flags: int = 0) -> RtDenoiseParams:
+        return RtDenoiseParams(int(self.iterations), float(self.sigma_color), float(self.sigma_normal),
+                               float(self.sigma_plane), int(self.flags) | int(extra_flags))
+
+
 _lib = None
 _variants: dict = {}
 
@@ -270,6 +293,11 @@ def _bind(L: C.CDLL) -> C.CDLL:
         L.rt_first_hit_device.argtypes = [vp, fpp, vp]
         L.rt_pick.argtypes = [vp, fpp, C.c_int32, C.c_int32, C.POINTER(RtHit)]
         L.rt_get_triangle_material.argtypes = [vp, C.c_int32, C.POINTER(RtMaterial), _i32p]
+    if hasattr(L, "rt_denoise"):  # RT_HAS_DENOISE (an addition within ABI 7, found by symbol)
+        fpp, dpp = C.POINTER(RtFrameParams), C.POINTER(RtDenoiseParams)
+        L.rt_denoise_default_params.argtypes = [dpp]
+        L.rt_denoise_async.argtypes = [vp, fpp, dpp, vp, vp, C.POINTER(vp)]
+        L.rt_denoise.argtypes = [vp, fpp, dpp, _f32p]
     return L
 
 
@@ -505,6 +533,31 @@ class Renderer:
         self._check(self._L.rt_display_fetch(self._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_uint8))),
                     "rt_display_fetch")
         return out
+
+    # ---------------------------------------------------------------- denoiser
+    def denoise(self, params: FrameParams, dp: Optional[DenoiseParams] = None) -> np.ndarray:
+        """rt_denoise: the accumulation through the edge-avoiding a-trous filter, guided by the
+        first-hit frame of `params`' camera: (H, W, 3) float32, row 0 = bottom.  The accumulation,
+        LoopNum and the stats are left as they were."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        p, d = params.to_c(), (dp or DenoiseParams()).to_c()
+        self._check(self._L.rt_denoise(self._h, C.byref(p), C.byref(d), _fp(out)), "rt_denoise")
+        return out
+
+    def denoise_async(self, params: FrameParams, dp: Optional[DenoiseParams] = None, frame_ptr: Optional[int] = None,
+                      hits_ptr: Optional[int] = None, reuse_guides: bool = False) -> int:
+        """rt_denoise_async: enqueue the filter on the ctx stream and return the device pointer of the
+        context-owned output frame (W*H*3 floats; pass it to tonemap / tonemap_async as frame_ptr;
+        valid in stream order until the next denoise call or resize).  frame_ptr: a W*H*3 float
+        device frame instead of the accumulation; hits_ptr: a first_hit_device buffer instead of the
+        library's own trace; reuse_guides: keep the previous call's guides (same camera, scene,
+        materials and size)."""
+        p = params.to_c()
+        d = (dp or DenoiseParams()).to_c(RT_DENOISE_REUSE_GUIDES if reuse_guides else 0)
+        out = C.c_void_p()
+        self._check(self._L.rt_denoise_async(self._h, C.byref(p), C.byref(d), C.c_void_p(frame_ptr) if frame_ptr else None,
+                                             C.c_void_p(hits_ptr) if hits_ptr else None, C.byref(out)), "rt_denoise_async")
+        return out.value or 0
 
     # ------------------------------------------------------------- ray queries
     def trace_rays(self, origins, dirs, kind: str = "closest", no_cull: bool = False) -> np.ndarray:

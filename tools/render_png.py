@@ -24,6 +24,7 @@ ap.add_argument("--height", type=int, default=0)
 ap.add_argument("--no-tonemap", action="store_true", help="enableToneMapping off: the screen blit")
 ap.add_argument("--no-gamma", action="store_true", help="enableGammaCorrection off")
 ap.add_argument("--brdf", action="store_true", help="enableBSDF off")
+ap.add_argument("--denoise", action="store_true", help="show the frame through rt_denoise (default parameters)")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
 
@@ -39,7 +40,7 @@ t = time.time()
 st = r.render(fp, cf.rand_origins(a.spp))
 dt = time.time() - t
 flags = (0 if a.no_tonemap else RT_DISPLAY_TONEMAP) | (0 if a.no_gamma else RT_DISPLAY_GAMMA)
-img = r.tonemap(flags)
+img = r.tonemap(flags, frame_ptr=r.denoise_async(fp) if a.denoise else None)
 Path(a.out).parent.mkdir(parents=True, exist_ok=True)
 sl.write_png(a.out, img)
 print(f"{a.config} {W}x{H} {a.spp} spp in {dt:.2f} s ({st['rays'] / dt / 1e6:.0f} Mrays/s) -> {a.out}")
