@@ -59,6 +59,9 @@
  *    The display denoiser (RT_HAS_DENOISE: rt_denoise_params, RT_DENOISE_*, rt_denoise_default_params,
  *    rt_denoise_async, rt_denoise) is an addition within ABI 7: nothing else changed, the version
  *    stays 7, and a binding finds it by symbol (a library built before it lacks rt_denoise).
+ *    The temporal stage of the displayed frame (RT_HAS_TEMPORAL: rt_temporal_params, RT_TEMPORAL_*,
+ *    rt_temporal_default_params, rt_temporal_async, rt_temporal, rt_temporal_history) is one more
+ *    addition within ABI 7, found the same way.
  * A binding checks rt_abi_version() at load time. */
 #define RT_ABI_VERSION 7
 #define RT_HAS_DENOISE 1
@@ -373,14 +376,14 @@ int rt_get_triangle_material(rt_ctx* ctx, int32_t triangle, rt_material* out, in
  * bit (they show the environment, which carries no noise); a non-finite pixel is never a source and
  * is filled from its neighbours by the geometric weights alone.
  * Out of scope: multi-rank contexts (a rank has guides for its own pixels only: RT_ERR_STATE when
- * world != 1), temporal reprojection, variance estimation, albedo demodulation. */
+ * world != 1), variance estimation, albedo demodulation (temporal reprojection: rt_temporal*, below). */
 typedef struct rt_denoise_params {
   int32_t iterations;               /* 1..5 */
   float sigma_color, sigma_normal, sigma_plane;   /* each finite and > 0 */
   int32_t flags;                    /* RT_DENOISE_* */
 } rt_denoise_params;                /* 20 bytes */
 /* REUSE_GUIDES: use the guides (normal, position, depth, material per pixel) of this context's
- * previous denoise call; the caller asserts that the camera, scene, materials and size are
+ * previous denoise or temporal call; the caller asserts that the camera, scene, materials and size are
  * unchanged since.  fp and hits_dev are ignored. */
 enum { RT_DENOISE_REUSE_GUIDES = 1 };
 /* The defaults: 5 iterations, sigma_color 1.0, sigma_normal 0.3, sigma_plane 0.01, flags 0. */
@@ -404,6 +407,77 @@ int rt_denoise_async(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_pa
 /* The same on this context's accumulation with the library's own first-hit trace (RT:1519),
  * synchronous: rgb_out_host = width*height*3 floats, RT_LAYOUT_FRAME order (row 0 = bottom). */
 int rt_denoise(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_params* dp, float* rgb_out_host);
+
+/* ---- Temporal accumulation of the displayed frame (RT_HAS_TEMPORAL, within ABI 7; no counterpart in
+ * the reference, where LoopNum = 0 starts the image again from nothing, main.cpp:326).  The context
+ * keeps a display history per pixel: colour, history length n, the two guide texels of the denoiser
+ * ({N, material or -1 for a camera miss}, {P, 1/t}) and the camera they were seen from.  A call
+ * reprojects that history into the current view through the current first-hit frame, rejects what
+ * is not the same surface, and blends the input frame into it, weighted by sample counts.  Like the
+ * denoiser it is a post-process of the displayed frame, between rendering and rt_denoise_async or
+ * rt_tonemap(_async): LoopNum, the accumulation, the path state, rt_order_work's order and every
+ * rt_stats field stay as they were.  All arithmetic is fp32 in a fixed order (DESIGN.md §4;
+ * tests/temporal_model.py is the same stage in numpy, and the two agree bit for bit).
+ * Per pixel, RT_LAYOUT_FRAME order, with input colour c, guides {N, M}, {P, 1/t}, S = samples:
+ *   miss (M == -1)  out = c, n_out = 0 (the environment carries no noise); never a history source.
+ *   hit             d = P - position', require d.front' > 0; k = (lbc'.front') / (d.front'),
+ *                   a = k (d.right') - lbc'.right', b = k (d.up') - lbc'.up',
+ *                   x = a / (2 half_w') * W - 0.5, y = b / (2 half_h') * H - 0.5 (primed: the history's
+ *                   rt_frame_params).  This inverts the camera ray of RT:1520-1527 under the
+ *                   assumption that front', right' and up' are unit length and orthogonal, as
+ *                   Camera.h:160-174 produces them.  The four bilinear taps (floor x + i, floor y + j)
+ *                   count when they lie in the frame, a history exists for this size, their n > 0,
+ *                   their colour is finite, their material is M, |N - Nq|^2 <= sigma_normal^2 and
+ *                   |N . (Pq - P)| / t <= sigma_plane.  With sw the counting taps' weight:
+ *                   h = sum(w cq) / sw, n_h = sum(w nq) / sw when sw > 0, else no history.
+ *   blend           history and finite c: n_out = min(n_h + S, max_history), alpha = min(S / n_out, 1),
+ *                   out = h + alpha (c - h).  No history: out = c, n_out = min(S, max_history).
+ *                   Non-finite c: out = h, n_out = n_h with history, else out = c, n_out = 0 (never a
+ *                   source; the denoiser fills it).
+ * RT_TEMPORAL_ADVANCE: the previous call's output (colours, lengths, guides, camera) becomes the
+ * history before this call runs (buffers change roles, nothing is copied).  Without it the history
+ * stays and this call's output replaces the previous call's as the candidate, so a still camera
+ * does not count the accumulation's samples twice: while LoopNum grows the display is
+ * (n H + k acc_k) / (n + k) against a frozen H.  Pass ADVANCE on the first display after the
+ * accumulation restarted.  RT_TEMPORAL_RESET drops history and candidate before the call;
+ * rt_resize and rt_set_scene drop them too.
+ * Out of scope: motion of scene objects, view-dependent (specular) reprojection, variance
+ * estimation, multi-rank contexts (RT_ERR_STATE when world != 1). */
+#define RT_HAS_TEMPORAL 1
+typedef struct rt_temporal_params {
+  int32_t samples;                  /* >= 1: samples per pixel in the input frame (LoopNum) */
+  int32_t max_history;              /* >= 1: cap on a pixel's history length */
+  float sigma_normal, sigma_plane;  /* each finite and > 0 */
+  int32_t flags;                    /* RT_TEMPORAL_* */
+} rt_temporal_params;               /* 20 bytes */
+/* REUSE_GUIDES: the current guides are those of this context's previous denoise or temporal call (the
+ * same assertion as RT_DENOISE_REUSE_GUIDES, which in turn accepts a temporal call's guides: the
+ * chain temporal -> denoise -> tonemap traces the first-hit frame once per view); hits_dev is
+ * ignored. */
+enum { RT_TEMPORAL_ADVANCE = 1, RT_TEMPORAL_REUSE_GUIDES = 2, RT_TEMPORAL_RESET = 4 };
+/* The defaults: samples 1, max_history 32, sigma_normal 0.3, sigma_plane 0.01, flags 0. */
+int rt_temporal_default_params(rt_temporal_params* tp);
+/* Enqueue the stage on the ctx stream, after the render calls queued before it (pipelined ones
+ * included); a render call queued afterwards blends only after the stage has read the
+ * accumulation.  frame_in_device, hits_dev: as for rt_denoise_async (NULL: this context's
+ * accumulation; NULL: the library traces the first-hit frame for fp).  fp is never ignored: its
+ * camera is kept with the output.  *frame_out_device receives the context-owned output frame
+ * (width*height*3 floats, RT_LAYOUT_FRAME order), valid in stream order until the next temporal
+ * call, rt_resize or rt_destroy; it can be passed to rt_denoise_async as frame_in_device or to
+ * rt_tonemap(_async) as frame_device.  The first temporal call allocates the denoiser's buffers
+ * (above) and, beside them, two {r, g, b, n} frames, two more guide pairs and the output: 108 B per
+ * pixel; dropped and re-sized by rt_resize, freed by rt_destroy.
+ * RT_ERR_ARG: a null pointer, samples < 1, max_history < 1, a sigma that is not finite and > 0,
+ * unknown flags, a non-finite camera.  RT_ERR_STATE: before rt_set_scene or rt_resize; a context with
+ * world != 1; RT_TEMPORAL_REUSE_GUIDES when no guides exist for the current size. */
+int rt_temporal_async(rt_ctx* ctx, const rt_frame_params* fp, const rt_temporal_params* tp,
+                      const float* frame_in_device, const void* hits_dev, float** frame_out_device);
+/* The same on this context's accumulation (first-hit frame: the library's own trace, or the
+ * previous call's guides with REUSE_GUIDES), synchronous: rgb_out_host = width*height*3 floats. */
+int rt_temporal(rt_ctx* ctx, const rt_frame_params* fp, const rt_temporal_params* tp, float* rgb_out_host);
+/* The history lengths n_out of the last temporal call's output: width*height floats,
+ * RT_LAYOUT_FRAME order; synchronous.  RT_ERR_STATE when there is none (no call yet, or dropped). */
+int rt_temporal_history(rt_ctx* ctx, float* n_out_host);
 
 #ifdef __cplusplus
 }

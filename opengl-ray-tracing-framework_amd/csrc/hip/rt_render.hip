@@ -22,6 +22,7 @@
 #include "rt_wavefront.h"
 #include "rt_query.h"
 #include "rt_denoise.h"
+#include "rt_temporal.h"
 
 #ifndef RT_SPLIT_KINDS  // bulk groups trace shadow rays and continuations in launches of their own (round 6)
 #define RT_SPLIT_KINDS 1
@@ -251,8 +252,23 @@ struct rt_ctx {
     float4* g1 = nullptr;                 //        {P.xyz, 1/t}
     float4* hits = nullptr;               // the library's own first-hit frame (rt_hit, local-tile layout)
     float* out = nullptr;                 // the output frame, W*H*3 floats
-    bool guides = false;                  // g0 / g1 hold a denoise call's guides for the current size
+    bool guides = false;                  // g0 / g1 hold a denoise or temporal call's guides for the current size
   } dn;
+  // The display history (rt_temporal*; rt_temporal.h), allocated by the first temporal call,
+  // dropped with the denoiser's buffers.  Nothing is copied when a call's output becomes the
+  // history: the colour frames and the guide pairs change roles.  dn.g0 / dn.g1 are the current
+  // guides and point at one of the three pairs (gp[0] is the denoiser's own); a fresh pack goes to
+  // a pair that neither the history nor a live candidate holds.
+  struct Temporal {
+    void* mem = nullptr;
+    float4* col[2] = {nullptr, nullptr};  // {r, g, b, n}: the history and the candidate (the last output)
+    float4* gp[3][2] = {};                // guide pairs {g0, g1}
+    float* out = nullptr;                 // the output frame, W*H*3 floats
+    int hist = -1, cand = -1;             // index into col; -1: none
+    int hist_g = -1, cand_g = -1;         // their guide pairs
+    rt_frame_params hist_fp{}, cand_fp{}; // the cameras they were seen from
+    void drop() { hist = cand = hist_g = cand_g = -1; }
+  } tp;
 };
 
 namespace {
@@ -744,6 +760,7 @@ int rt_destroy(rt_ctx* c) {
   if (c->q.mem) (void)hipFree(c->q.mem);
   dfree(c->q.d_ovf);
   if (c->dn.mem) (void)hipFree(c->dn.mem);
+  if (c->tp.mem) (void)hipFree(c->tp.mem);
   dfree(c->d_disp);
   dfree(c->d_gather);
   for (auto& m : c->rccl_comms) (void)ncclCommDestroy(m);
@@ -774,6 +791,7 @@ int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   // the old buffers no longer describe a scene from here on: a failure below leaves the context
   // without one (renders and queries then refuse) rather than with a mix of old and new buffers
   c->scene_set = false;
+  c->tp.drop();  // the display history shows another scene
   int rc;
   if ((rc = upload(c, (void**)&c->d_qnodes, k.qnodes.data(), k.qnodes.size() * sizeof(scn::WNode)))) return rc;
   if ((rc = upload(c, (void**)&c->d_nodes, k.nodes.data(), k.nodes.size() * sizeof(scn::BNode)))) return rc;
@@ -872,6 +890,8 @@ static int apply_tiling(rt_ctx* c, int width, int height, const rt_tiling& tl, s
   c->frame_set = false;
   if (c->dn.mem) (void)hipFree(c->dn.mem);  // the denoiser's frames and guides are the old size's
   c->dn = rt_ctx::Denoise{};
+  if (c->tp.mem) (void)hipFree(c->tp.mem);  // and so is the display history
+  c->tp = rt_ctx::Temporal{};
   c->W = width; c->H = height;
   c->tile_w = tl.tile_w; c->tile_h = tl.tile_h; c->rank = tl.rank; c->world = tl.world;
   c->tiles_x = (width + tl.tile_w - 1) / tl.tile_w;
@@ -2460,6 +2480,55 @@ int reserve_denoise(rt_ctx* c) {
 
 bool dn_sigma_ok(float s) { return std::isfinite(s) && s > 0.0f; }
 
+// The display history's buffers for the current frame size (after reserve_denoise: gp[0] is the
+// denoiser's guide pair)
+int reserve_temporal(rt_ctx* c) {
+  rt_ctx::Temporal& t = c->tp;
+  if (t.mem) return RT_OK;
+  const size_t npx = (size_t)c->W * c->H;
+  auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t bytes = 6 * pad(npx * 16) + pad(npx * 12);
+  const hipError_t me = hipMalloc(&t.mem, bytes);
+  if (me == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    t.mem = nullptr;
+    return fail(c, RT_ERR_NOMEM, "display history does not fit in device memory");
+  }
+  HIPCHK(c, me);
+  char* p = static_cast<char*>(t.mem);
+  auto carve = [&](size_t b) { char* r = p; p += pad(b); return r; };
+  t.col[0] = (float4*)carve(npx * 16);
+  t.col[1] = (float4*)carve(npx * 16);
+  t.gp[0][0] = c->dn.g0;
+  t.gp[0][1] = c->dn.g1;
+  for (int k = 1; k < 3; k++)
+    for (int j = 0; j < 2; j++) t.gp[k][j] = (float4*)carve(npx * 16);
+  t.out = (float*)carve(npx * 12);
+  t.drop();
+  return RT_OK;
+}
+
+// The guide pair dn.g0 / dn.g1 point at (0, the denoiser's own, without a display history)
+int tp_current_pair(const rt_ctx* c) {
+  for (int k = 1; k < 3; k++)
+    if (c->tp.mem && c->tp.gp[k][0] == c->dn.g0) return k;
+  return 0;
+}
+
+// Before a fresh pack of the current guides: point dn.g0 / dn.g1 at a pair that the history does
+// not hold, nor (keep_cand) the candidate; the pair they point at when that one is free.  Without a
+// display history the denoiser's own pair stays.  Returns the pair's index.
+int tp_guides_target(rt_ctx* c, bool keep_cand) {
+  rt_ctx::Temporal& t = c->tp;
+  if (!t.mem) return 0;
+  int cur = tp_current_pair(c);
+  auto taken = [&](int k) { return k == t.hist_g || (keep_cand && k == t.cand_g); };
+  for (int k = 0; k < 3 && taken(cur); k++) cur = k;
+  c->dn.g0 = t.gp[cur][0];
+  c->dn.g1 = t.gp[cur][1];
+  return cur;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2493,6 +2562,7 @@ int rt_denoise_async(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_para
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = reserve_denoise(c)) return rc;
   rt_ctx::Denoise& d = c->dn;
+  if (!reuse) tp_guides_target(c, true);
   if (trace) {
     d.guides = false;  // (they are being replaced: a failure below leaves none)
     if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
@@ -2552,6 +2622,119 @@ int rt_denoise(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_params* dp
   if (int rc = rt_denoise_async(c, fp, dp, nullptr, nullptr, &out)) return rc;
   HIPCHK(c, hipMemcpyAsync(rgb_out_host, out, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ----------------------------------------------------------------------------- display history
+int rt_temporal_default_params(rt_temporal_params* tp) {
+  if (!tp) return RT_ERR_ARG;
+  tp->samples = 1;
+  tp->max_history = 32;
+  tp->sigma_normal = 0.3f;
+  tp->sigma_plane = 0.01f;
+  tp->flags = 0;
+  return RT_OK;
+}
+
+int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_params* tp, const float* frame_in_device,
+                      const void* hits_dev, float** frame_out_device) {
+  if (!c) return RT_ERR_ARG;
+  if (!tp || !frame_out_device) return fail(c, RT_ERR_ARG, "null parameters or output");
+  if (!fp) return fail(c, RT_ERR_ARG, "null frame parameters");  // (never ignored: the output is stored with its camera)
+  if (tp->samples < 1) return fail(c, RT_ERR_ARG, "samples < 1");
+  if (tp->max_history < 1) return fail(c, RT_ERR_ARG, "max_history < 1");
+  if (!dn_sigma_ok(tp->sigma_normal) || !dn_sigma_ok(tp->sigma_plane)) return fail(c, RT_ERR_ARG, "a sigma is not finite and > 0");
+  if (tp->flags & ~(RT_TEMPORAL_ADVANCE | RT_TEMPORAL_REUSE_GUIDES | RT_TEMPORAL_RESET)) return fail(c, RT_ERR_ARG, "unknown flags");
+  const bool reuse = (tp->flags & RT_TEMPORAL_REUSE_GUIDES) != 0;
+  const bool trace = !reuse && !hits_dev;
+  if (!c->scene_set || !c->frame_set) return fail(c, RT_ERR_STATE, "rt_set_scene and rt_resize first");
+  if (c->world != 1) return fail(c, RT_ERR_STATE, "a multi-rank context has guides for its own pixels only");
+  if (reuse && !(c->dn.mem && c->dn.guides)) return fail(c, RT_ERR_STATE, "no guides of an earlier denoise or temporal call for this size");
+  if (int rc = camera_args(c, fp, true)) return rc;
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(fp->front[a])) return fail(c, RT_ERR_ARG, "non-finite camera");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = reserve_denoise(c)) return rc;
+  if (int rc = reserve_temporal(c)) return rc;
+  rt_ctx::Denoise& d = c->dn;
+  rt_ctx::Temporal& t = c->tp;
+  // The previous output changes roles: the history (ADVANCE), or nothing (this call's replaces it)
+  if (tp->flags & RT_TEMPORAL_RESET) {
+    t.drop();
+  } else if ((tp->flags & RT_TEMPORAL_ADVANCE) && t.cand >= 0) {
+    t.hist = t.cand;
+    t.hist_g = t.cand_g;
+    t.hist_fp = t.cand_fp;
+  }
+  t.cand = t.cand_g = -1;
+  const int pair = reuse ? tp_current_pair(c) : tp_guides_target(c, false);  // (the old candidate's is free)
+  if (trace) {
+    d.guides = false;  // (they are being replaced: a failure below leaves none)
+    if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
+  }
+  // The pack reads the accumulation on the ctx stream: ordering as in rt_denoise_async
+  const dim3 pgrid((c->W + 255) / 256, c->H);
+  const float4* tiles = frame_in_device ? nullptr : c->d_accum;
+  if (reuse)
+    hipLaunchKernelGGL(rtd::dn_pack<false>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device, (const float4*)nullptr,
+                       d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w, c->tile_h, c->tiles_x);
+  else
+    hipLaunchKernelGGL(rtd::dn_pack<true>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device,
+                       hits_dev ? (const float4*)hits_dev : d.hits, d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w,
+                       c->tile_h, c->tiles_x);
+  HIPCHK(c, hipGetLastError());
+  d.guides = true;
+  const int cand = t.hist == 0 ? 1 : 0;
+  rtd::TpCall T;
+  T.cur = d.col[0];
+  T.g0 = d.g0;
+  T.g1 = d.g1;
+  T.hc = t.hist >= 0 ? t.col[t.hist] : nullptr;
+  T.hg0 = t.hist >= 0 ? t.gp[t.hist_g][0] : nullptr;
+  T.hg1 = t.hist >= 0 ? t.gp[t.hist_g][1] : nullptr;
+  T.cand = t.col[cand];
+  T.out3 = t.out;
+  T.W = c->W;
+  T.H = c->H;
+  const rt_frame_params& h = t.hist_fp;  // (all zero without a history: not read)
+  memcpy(T.pos, h.position, 12); memcpy(T.front, h.front, 12); memcpy(T.right, h.right, 12);
+  memcpy(T.up, h.up, 12); memcpy(T.lbc, h.left_bottom_corner, 12);
+  T.tw = 2.0f * h.half_w;
+  T.th = 2.0f * h.half_h;
+  T.S = (float)tp->samples;
+  T.max_n = (float)tp->max_history;
+  T.sn2 = tp->sigma_normal * tp->sigma_normal;
+  T.sp = tp->sigma_plane;
+  const dim3 grid((unsigned)((c->W + rtd::kDnTW - 1) / rtd::kDnTW), (unsigned)((c->H + rtd::kDnTH - 1) / rtd::kDnTH));
+  hipLaunchKernelGGL(rtd::tp_resolve, grid, dim3(256), 0, c->stream, T);
+  HIPCHK(c, hipGetLastError());
+  t.cand = cand;
+  t.cand_g = pair;
+  t.cand_fp = *fp;
+  *frame_out_device = t.out;
+  return RT_OK;
+}
+
+int rt_temporal(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_params* tp, float* rgb_out_host) {
+  if (!c) return RT_ERR_ARG;
+  if (!rgb_out_host) return fail(c, RT_ERR_ARG, "null output");
+  float* out = nullptr;
+  if (int rc = rt_temporal_async(c, fp, tp, nullptr, nullptr, &out)) return rc;
+  HIPCHK(c, hipMemcpyAsync(rgb_out_host, out, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_temporal_history(rt_ctx* c, float* n_out_host) {
+  if (!c) return RT_ERR_ARG;
+  if (!n_out_host) return fail(c, RT_ERR_ARG, "null output");
+  if (!c->tp.mem || c->tp.cand < 0) return fail(c, RT_ERR_STATE, "no temporal call for the current size and scene");
+  const size_t npx = (size_t)c->W * c->H;
+  std::vector<float> buf(4 * npx);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(buf.data(), c->tp.col[c->tp.cand], npx * 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < npx; i++) n_out_host[i] = buf[4 * i + 3];
   return RT_OK;
 }
 

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import configs as cf
 from . import scene_lib as sl
-from .renderer import RT_DISPLAY_GAMMA, RT_DISPLAY_TONEMAP, FrameParams, Renderer
+from .renderer import RT_DISPLAY_GAMMA, RT_DISPLAY_TONEMAP, FrameParams, Renderer, TemporalParams
 
 f32 = np.float32
 
@@ -116,10 +116,11 @@ class Settings:
     max_bounce: int = 8
     max_iterations: int = 3000
     enable_denoise: bool = False  # (no counterpart in the reference) rt_denoise before the display pass
+    enable_temporal: bool = False  # (likewise) rt_temporal before both: the display history follows the camera
 
 
 # OnGUI controls that restart the accumulation (main.cpp:343-368, :408); tone mapping / gamma
-# (main.cpp:373-374) and the denoiser only change the display pass
+# (main.cpp:373-374), the denoiser and the temporal stage only change the display pass
 RESETTING = {"enable_env_map", "env_intensity", "env_angle", "enable_mis", "max_bounce", "max_iterations",
              "enable_bsdf"}
 
@@ -173,6 +174,9 @@ class Session:
         # the denoiser's guides (first-hit frame) are those of this session's last denoise call and
         # still describe the view: no r.reset() (camera, settings, materials) or resize since
         self._guides_current = False
+        # the next temporal call is the first display since the accumulation restarted (or since the
+        # stage was last on): the previous call's output becomes the history (RT_TEMPORAL_ADVANCE)
+        self._advance = True
 
     # main.cpp:296-318
     def _mouse(self, xpos: float, ypos: float, rmb: bool) -> None:
@@ -203,8 +207,9 @@ class Session:
         if inp.resize is not None:  # framebuffer_size_callback (main.cpp:289-294)
             self.width, self.height = inp.resize
             self.camera.process_screen_ratio(self.width, self.height)
-            self.r.resize(self.width, self.height)
+            self.r.resize(self.width, self.height)  # (drops the display history)
             self._guides_current = False
+            self._advance = True
         for x, y, rmb in inp.mouse:
             self._mouse(x, y, rmb)
         held = {k.upper() for k in inp.keys}
@@ -232,6 +237,7 @@ class Session:
         if self.camera.take_reset() or reset:
             self.r.reset()
             self._guides_current = False
+            self._advance = True
         fp = self.frame_params()
         picked = self._pick(fp, *inp.pick) if inp.pick is not None else None
         ro = self._rand[self.frame:self.frame + 1]
@@ -248,11 +254,19 @@ class Session:
         flags = (RT_DISPLAY_TONEMAP if s.enable_tone_mapping else 0) | \
                 (RT_DISPLAY_GAMMA if s.enable_tone_mapping and s.enable_gamma_correction else 0)
         out["display_flags"] = flags
-        # the displayed frame: the accumulation itself (frame_ptr omitted: today's calls), or its
-        # denoised copy on the device, queued behind the frame on the renderer's stream
+        # the displayed frame: the accumulation itself (frame_ptr omitted: today's calls), or a copy
+        # on the device, queued behind the frame on the renderer's stream: blended into the
+        # reprojected display history, denoised, or both (one first-hit trace per view)
         shown = {}
+        if not s.enable_temporal:
+            self._advance = True
+        elif display:
+            shown["frame_ptr"] = self.r.temporal_async(fp, TemporalParams(samples=max(1, out["loop_num"])),
+                                                       advance=self._advance, reuse_guides=self._guides_current)
+            self._advance = False
+            self._guides_current = True
         if display and s.enable_denoise:
-            shown["frame_ptr"] = self.r.denoise_async(fp, reuse_guides=self._guides_current)
+            shown["frame_ptr"] = self.r.denoise_async(fp, reuse_guides=self._guides_current, **shown)
             self._guides_current = True
         if self.in_flight == 1:
             if display:

@@ -49,10 +49,13 @@ ABI_SYMBOLS = (
     "rt_trace_rays", "rt_trace_rays_device", "rt_camera_rays", "rt_first_hit", "rt_first_hit_device", "rt_pick",
     "rt_get_triangle_material",
     "rt_denoise_default_params", "rt_denoise_async", "rt_denoise",
+    "rt_temporal_default_params", "rt_temporal_async", "rt_temporal", "rt_temporal_history",
 )
 RT_DISPLAY_TONEMAP, RT_DISPLAY_GAMMA = 1, 2
 RT_HAS_DENOISE = 1
 RT_DENOISE_REUSE_GUIDES = 1
+RT_HAS_TEMPORAL = 1
+RT_TEMPORAL_ADVANCE, RT_TEMPORAL_REUSE_GUIDES, RT_TEMPORAL_RESET = 1, 2, 4
 
 
 class RtMaterial(C.Structure):
@@ -198,6 +201,27 @@ class DenoiseParams:
                                float(self.sigma_plane), int(self.flags) | int(extra_flags))
 
 
+class RtTemporalParams(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("max_history", C.c_int32), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float), ("flags", C.c_int32)]
+
+
+@dataclasses.dataclass
+class TemporalParams:
+    """rt_temporal_params with rt_temporal_default_params' values: the samples per pixel of the input
+    frame (LoopNum), the cap of a pixel's history length, and the normal and plane-distance bounds
+    of the same-surface test (the denoiser's sigmas)."""
+    samples: int = 1
+    max_history: int = 32
+    sigma_normal: float = 0.3
+    sigma_plane: float = 0.01
+    flags: int = 0
+
+    def to_c(self, extra_flags: int = 0) -> RtTemporalParams:
+        return RtTemporalParams(int(self.samples), int(self.max_history), float(self.sigma_normal),
+                                float(self.sigma_plane), int(self.flags) | int(extra_flags))
+
+
 _lib = None
 _variants: dict = {}
 
@@ -298,6 +322,12 @@ def _bind(L: C.CDLL) -> C.CDLL:
         L.rt_denoise_default_params.argtypes = [dpp]
         L.rt_denoise_async.argtypes = [vp, fpp, dpp, vp, vp, C.POINTER(vp)]
         L.rt_denoise.argtypes = [vp, fpp, dpp, _f32p]
+    if hasattr(L, "rt_temporal"):  # RT_HAS_TEMPORAL (likewise)
+        fpp, tpp = C.POINTER(RtFrameParams), C.POINTER(RtTemporalParams)
+        L.rt_temporal_default_params.argtypes = [tpp]
+        L.rt_temporal_async.argtypes = [vp, fpp, tpp, vp, vp, C.POINTER(vp)]
+        L.rt_temporal.argtypes = [vp, fpp, tpp, _f32p]
+        L.rt_temporal_history.argtypes = [vp, _f32p]
     return L
 
 
@@ -558,6 +588,44 @@ class Renderer:
         self._check(self._L.rt_denoise_async(self._h, C.byref(p), C.byref(d), C.c_void_p(frame_ptr) if frame_ptr else None,
                                              C.c_void_p(hits_ptr) if hits_ptr else None, C.byref(out)), "rt_denoise_async")
         return out.value or 0
+
+    # ---------------------------------------------------------------- display history
+    @staticmethod
+    def _temporal_flags(advance: bool, reuse_guides: bool, reset: bool) -> int:
+        return (RT_TEMPORAL_ADVANCE if advance else 0) | (RT_TEMPORAL_REUSE_GUIDES if reuse_guides else 0) | \
+               (RT_TEMPORAL_RESET if reset else 0)
+
+    def temporal(self, params: FrameParams, tp: Optional[TemporalParams] = None, advance: bool = False,
+                 reuse_guides: bool = False, reset: bool = False) -> np.ndarray:
+        """rt_temporal: the accumulation blended into the display history reprojected from the
+        previous view: (H, W, 3) float32, row 0 = bottom.  advance: the previous call's output
+        becomes the history first (the first display after the accumulation restarted).  The
+        accumulation, LoopNum and the stats are left as they were."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        p = params.to_c()
+        t = (tp or TemporalParams()).to_c(self._temporal_flags(advance, reuse_guides, reset))
+        self._check(self._L.rt_temporal(self._h, C.byref(p), C.byref(t), _fp(out)), "rt_temporal")
+        return out
+
+    def temporal_async(self, params: FrameParams, tp: Optional[TemporalParams] = None, frame_ptr: Optional[int] = None,
+                       hits_ptr: Optional[int] = None, advance: bool = False, reuse_guides: bool = False,
+                       reset: bool = False) -> int:
+        """rt_temporal_async: enqueue the stage on the ctx stream and return the device pointer of the
+        context-owned output frame (W*H*3 floats; pass it to denoise_async / tonemap / tonemap_async
+        as frame_ptr; valid in stream order until the next temporal call or resize).  frame_ptr,
+        hits_ptr, reuse_guides: as for denoise_async."""
+        p = params.to_c()
+        t = (tp or TemporalParams()).to_c(self._temporal_flags(advance, reuse_guides, reset))
+        out = C.c_void_p()
+        self._check(self._L.rt_temporal_async(self._h, C.byref(p), C.byref(t), C.c_void_p(frame_ptr) if frame_ptr else None,
+                                              C.c_void_p(hits_ptr) if hits_ptr else None, C.byref(out)), "rt_temporal_async")
+        return out.value or 0
+
+    def temporal_history(self) -> np.ndarray:
+        """rt_temporal_history: (H, W) float32 history lengths of the last temporal call's output."""
+        out = np.zeros((self.height, self.width), np.float32)
+        self._check(self._L.rt_temporal_history(self._h, _fp(out)), "rt_temporal_history")
+        return out
 
     # ------------------------------------------------------------- ray queries
     def trace_rays(self, origins, dirs, kind: str = "closest", no_cull: bool = False) -> np.ndarray:

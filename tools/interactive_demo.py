@@ -30,6 +30,8 @@ ap.add_argument("--png", action="store_true", help="write the displayed image of
 ap.add_argument("--no-display", action="store_true", help="skip the per-frame 8-bit read-back")
 ap.add_argument("--in-flight", type=int, default=1,
                 help="frames in flight (Session frames_in_flight: the GL frame queue; images unchanged)")
+ap.add_argument("--temporal", action="store_true", help="Settings.enable_temporal: the display history follows the camera")
+ap.add_argument("--denoise", action="store_true", help="Settings.enable_denoise: the à-trous filter before the display pass")
 a = ap.parse_args()
 
 cfg = cf.CONFIGS[a.config]
@@ -38,7 +40,8 @@ sd = cf.config_scene(a.config)
 r = Renderer(0)
 r.set_scene_soa(sd.soa, sd.nodes)
 r.set_env(*cf.load_env())
-s = ia.Session(r, W, H, frames_in_flight=a.in_flight)
+s = ia.Session(r, W, H, settings=ia.Settings(enable_temporal=a.temporal, enable_denoise=a.denoise),
+               frames_in_flight=a.in_flight)
 dt = 1.0 / 60.0
 phases = [
     ("still", lambda k: ia.Input()),
