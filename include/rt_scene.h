@@ -127,6 +127,31 @@ int rts_glibc_rand(unsigned int seed, int n, int* out);
  * reference's edge functions alone.  For tests: it replaces no reference interface. */
 int rts_tri_filter(const float* tri, int n_triangles, float* out, double* k, int32_t* flagged);
 
+/* The HIP path's carved device allocations (csrc/common/dev_layout.h; rt_render.hip places its
+ * arrays by the same code), for tests only: the layout `kind` for sizes n and m (below; m unused:
+ * any value) as n_spans arrays, at most cap, in the layout's own order.  A span starts off units
+ * from the allocation's start and holds `bytes` units (bytes; ints in the frame table, float4 in
+ * the camera table); host = the span it lies inside (-1: memory of its own); live = 0: a lean frame
+ * group has stopped using the array when pass 1 starts (path state alone).
+ *   PATH_STATE   n path slots, m = 1..4 sets.  Per set 32 spans: s0-s5, ra, rb, sa, sb, res, fin,
+ *                queue0/1, active0/1, queue_s0/1, hit, cnt, then the row arena's s0-s5, ra, rb, sa,
+ *                sb, res, rpath.  scalars = {total, bytes per set, slots, hit entries, arena rows,
+ *                bytes per slot, bytes per arena row}
+ *   QUERY        n rays: ra, rb, queue, res, d_in, d_out, cnt, zero.  scalars = {total, rays held}
+ *   DENOISE      n = W * H pixels, m pixels of the first-hit frame: col0, col1, g0, g1, hits, out
+ *   HISTORY      n = W * H pixels: col0, col1, the two guide pairs of its own, out
+ *   FRAME_TABLE  n frames: loop_num, rand_origin, sobol, blend_w.  scalars = {total, host copy}
+ *   CAMERA_TABLE n work items, m <= 8 pipeline sets: each set's directions, then each set's hit points
+ * scalars[8]: the allocation's total first, unused entries 0. */
+enum { RTS_LAYOUT_PATH_STATE = 0, RTS_LAYOUT_QUERY, RTS_LAYOUT_DENOISE, RTS_LAYOUT_HISTORY, RTS_LAYOUT_FRAME_TABLE,
+       RTS_LAYOUT_CAMERA_TABLE };
+typedef struct rts_dev_span {
+  uint64_t off, bytes;
+  int32_t host, live;
+} rts_dev_span;
+int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_dev_span* spans, int32_t cap,
+                   int32_t* n_spans);
+
 /* The HIP path's scene compiler (csrc/common/scene_compile.h; rt_set_scene uploads what the same
  * code returns): an rt_scene_soa (rt_abi.h), or the reference's encodings, -> the device arrays
  * and scalars.  A test and tooling interface: it replaces no reference interface.  options = four

@@ -35,6 +35,7 @@
 #define RT_SPLIT_CONT_FIRST 0  // C3 1 vs 0: -0.16% (profiles/r06_ab_split_knobs_C3.log)
 #endif
 #include "scene_compile.h"
+#include "dev_layout.h"
 
 using rtd::GNode;
 using rtd::KParams;
@@ -335,6 +336,23 @@ scn::Options scene_options() {
   return o;
 }
 
+// One block for a carved layout (dev_layout.h): RT_ERR_NOMEM with `what` when HBM cannot hold it
+int alloc_block(rt_ctx* c, void*& mem, size_t bytes, const char* what) {
+  const hipError_t me = hipMalloc(&mem, bytes);
+  if (me == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    mem = nullptr;
+    return fail(c, RT_ERR_NOMEM, what);
+  }
+  HIPCHK(c, me);
+  return RT_OK;
+}
+// p = the array of a layout at `at`
+template <typename P>
+void place(P& p, void* base, dvl::Span at) {
+  p = (P)(static_cast<char*>(base) + at.off);
+}
+
 int upload(rt_ctx* c, void** dst, const void* src, size_t bytes) {
   if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
   if (bytes == 0) return RT_OK;
@@ -621,21 +639,28 @@ void update_frames_cap(rt_ctx* c, size_t nv) {
   c->frames_cap = (int)std::max<size_t>(1, std::min<size_t>(RT_MAX_FRAMES_PER_LAUNCH, max_slots / std::max<size_t>(1, nv)));
 }
 
-// Rows of a set's row arena (WFParams::A) and of a group's share of it.  A row is 148 B: s0-s4
-// (80), s5 (8), ra + rb and sa + sb (48), res (8) and rpath (4).  A quarter of the slots (C3 keeps
-// about 11 % of them after pass 1, C4's glass view nearly half: that one falls back) is 37 B per
-// slot, which fits the 40 B per slot of the four slot arrays a lean group neither reads nor writes
-// from pass 1 on (s1: every kept path is PF_ZLO; s5, rb, sb: pass 1 has no s5 row and 16-B rays), and
-// once a group runs on the arena it touches no slot array but fin.  So the arena is carved from
-// those arrays: the path state stays at 184 B per slot and the frames per launch where they were.
-// (whole groups of 4 rows: every arena array starts 16-B aligned)
-size_t arena_rows(size_t slots) { return slots / 4 & ~size_t(3); }
-
-// Path-state buffers of the wavefront path: `paths` slots for each of the n_groups frame
-// groups, carved from one allocation (184 B per slot + counters; the row arena aliases four of the
-// slot arrays, arena_rows).  RT_ERR_NOMEM when HBM
+// Path-state buffers of the wavefront path: `paths` slots for each of the n_groups frame groups
+// and each set's row arena, laid out by dvl::path_state and dvl::arena.  RT_ERR_NOMEM when HBM
 // cannot hold them (the caller then runs fewer frames at a time).
 static_assert(rt_ctx::MAX_GROUPS <= 4, "rtd::GroupCounters holds 4 groups' counters");
+// dev_layout.h cannot see the kernels' types: its element sizes are theirs
+constexpr rtd::WFState* kWF = nullptr;  // (sizeof operands only)
+constexpr size_t slot_b(dvl::Slot s) { return dvl::kSlot[s].bytes; }
+constexpr size_t row_b(dvl::Row r) { return dvl::kArena[r].bytes; }
+static_assert(slot_b(dvl::S0) == sizeof(*kWF->s0) && slot_b(dvl::S1) == sizeof(*kWF->s1) && slot_b(dvl::S2) == sizeof(*kWF->s2) &&
+              slot_b(dvl::S3) == sizeof(*kWF->s3) && slot_b(dvl::S4) == sizeof(*kWF->s4) && slot_b(dvl::S5) == sizeof(*kWF->s5) &&
+              slot_b(dvl::RA) == sizeof(*kWF->ra) && slot_b(dvl::RB) == sizeof(*kWF->rb) && slot_b(dvl::SA) == sizeof(*kWF->sa) &&
+              slot_b(dvl::SB) == sizeof(*kWF->sb) && slot_b(dvl::RES) == 2 * sizeof(*kWF->res) && slot_b(dvl::FIN) == sizeof(*kWF->fin) &&
+              slot_b(dvl::QUEUE0) == 2 * sizeof(*kWF->queue[0]) && slot_b(dvl::QUEUE1) == 2 * sizeof(*kWF->queue[1]) &&
+              slot_b(dvl::ACTIVE0) == sizeof(*kWF->active[0]) && slot_b(dvl::ACTIVE1) == sizeof(*kWF->active[1]) &&
+              sizeof(*kWF->hit) == 4 && sizeof(*kWF->cnt) == 4 && dvl::kCntWords == rtd::kCntWords,
+              "dvl::kSlot holds the element sizes of rtd::WFState's slot arrays");
+static_assert(row_b(dvl::A_S0) == sizeof(*kWF->s0) && row_b(dvl::A_S1) == sizeof(*kWF->s1) && row_b(dvl::A_S2) == sizeof(*kWF->s2) &&
+              row_b(dvl::A_S3) == sizeof(*kWF->s3) && row_b(dvl::A_S4) == sizeof(*kWF->s4) && row_b(dvl::A_S5) == sizeof(*kWF->s5) &&
+              row_b(dvl::A_RA) == sizeof(*kWF->ra) && row_b(dvl::A_RB) == sizeof(*kWF->rb) && row_b(dvl::A_SA) == sizeof(*kWF->sa) &&
+              row_b(dvl::A_SB) == sizeof(*kWF->sb) && row_b(dvl::A_RES) == 2 * sizeof(*kWF->res) && row_b(dvl::A_RPATH) == sizeof(*kWF->rpath),
+              "dvl::kArena holds the element sizes of the row arena's arrays");
+static_assert(dvl::kRayBytes == sizeof(rt_ray) && dvl::kHitBytes == sizeof(rt_hit), "dvl's staging records are rt_abi.h's");
 int alloc_wavefront(rt_ctx* c, size_t paths) {
   if (c->wf_mem && c->wf_paths >= paths) return RT_OK;
   if (c->wf_mem) {  // grow: earlier launches on the streams may still read the old state
@@ -643,50 +668,37 @@ int alloc_wavefront(rt_ctx* c, size_t paths) {
     (void)hipFree(c->wf_mem);
     c->wf_mem = nullptr;
   }
-  const size_t P = std::max<size_t>(paths, 64);
-  // the hit-pixel list: one entry per work item of a group of >= 64 frames (wf_cam_classify)
-  const size_t hit_cap = P / 64 + 64;
-  const size_t per = P * (5 * 16 + sizeof(*c->wfg[0].s5) + 2 * (16 + 8) + 2 * 4 + 16 + 2 * 8 + 2 * 4) + hit_cap * 4 + 32768;  // + carve padding
-  const hipError_t me = hipMalloc(&c->wf_mem, per * c->n_groups);
-  if (me == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    c->wf_mem = nullptr;
-    c->wf_paths = 0;
-    return fail(c, RT_ERR_NOMEM, "path state does not fit in device memory");
+  const dvl::PathState L = dvl::path_state(paths, c->n_groups);
+  const dvl::Arena A = dvl::arena(L);
+  if (int rc = alloc_block(c, c->wf_mem, L.total, "path state does not fit in device memory")) {
+    if (rc == RT_ERR_NOMEM) c->wf_paths = 0;
+    return rc;
   }
-  HIPCHK(c, me);
-  char* p = static_cast<char*>(c->wf_mem);
-  auto carve = [&](size_t n) { char* q = p; p += (n + 255) & ~size_t(255); return q; };
   for (int g = 0; g < c->n_groups; g++) {
+    char* const set = static_cast<char*>(c->wf_mem) + L.set(g);
     rtd::WFState& w = c->wfg[g];
-    w.s0 = (float4*)carve(P * 16); w.s1 = (float4*)carve(P * 16); w.s2 = (float4*)carve(P * 16);
-    w.s3 = (float4*)carve(P * 16); w.s4 = (float4*)carve(P * 16); w.s5 = (decltype(w.s5))carve(P * sizeof(*w.s5));
-    w.ra = (float4*)carve(P * 16); w.rb = (float2*)carve(P * 8);
-    w.sa = (float4*)carve(P * 16); w.sb = (float2*)carve(P * 8);
-    w.res = (int*)carve(P * 8);
-    w.fin = (float4*)carve(P * 16);
-    w.queue[0] = (int*)carve(P * 8); w.queue[1] = (int*)carve(P * 8);
-    w.queue_s[0] = w.queue[0] + P; w.queue_s[1] = w.queue[1] + P;  // (split queues: one entry per path each)
-    w.active[0] = (int*)carve(P * 4); w.active[1] = (int*)carve(P * 4);
-    w.hit = (int*)carve(hit_cap * 4);
-    w.cnt = (unsigned int*)carve(rtd::kCntWords * 4);
-    // the row arena: s0-s3 in s1's 16 P bytes, s4 and ra in s5's 8 P, sa, s5 and rb in rb's 8 P,
-    // sb, res and rpath in sb's 8 P (R <= P / 4 rows); everything else as the slot-indexed state
-    const size_t R = arena_rows(P);
+    auto slot = [&](auto& p, dvl::Slot s) { place(p, set, L.arr[s]); };
+    slot(w.s0, dvl::S0); slot(w.s1, dvl::S1); slot(w.s2, dvl::S2); slot(w.s3, dvl::S3); slot(w.s4, dvl::S4); slot(w.s5, dvl::S5);
+    slot(w.ra, dvl::RA); slot(w.rb, dvl::RB); slot(w.sa, dvl::SA); slot(w.sb, dvl::SB);
+    slot(w.res, dvl::RES); slot(w.fin, dvl::FIN);
+    for (int k = 0; k < 2; k++) {
+      slot(w.queue[k], dvl::Slot(dvl::QUEUE0 + k));
+      place(w.queue_s[k], set, L.queue_s[k]);
+      slot(w.active[k], dvl::Slot(dvl::ACTIVE0 + k));
+    }
+    place(w.hit, set, L.hit);
+    place(w.cnt, set, L.cnt);
+    // the row arena: its own rows of the path state, everything else as the slot-indexed state
     rtd::WFState& a = c->wfa[g];
     a = w;
-    char* q = (char*)w.s1;
-    a.s0 = (float4*)q; a.s1 = (float4*)(q + 16 * R); a.s2 = (float4*)(q + 32 * R); a.s3 = (float4*)(q + 48 * R);
-    q = (char*)w.s5;
-    a.s4 = (float4*)q; a.ra = (float4*)(q + 16 * R);
-    q = (char*)w.rb;
-    a.sa = (float4*)q; a.s5 = (decltype(a.s5))(q + 16 * R); a.rb = (float2*)(q + 24 * R);
-    q = (char*)w.sb;
-    a.sb = (float2*)q; a.res = (int*)(q + 8 * R); a.rpath = (unsigned int*)(q + 16 * R);
+    auto row = [&](auto& p, dvl::Row r) { place(p, set, A.arr[r]); };
+    row(a.s0, dvl::A_S0); row(a.s1, dvl::A_S1); row(a.s2, dvl::A_S2); row(a.s3, dvl::A_S3); row(a.s4, dvl::A_S4); row(a.s5, dvl::A_S5);
+    row(a.ra, dvl::A_RA); row(a.rb, dvl::A_RB); row(a.sa, dvl::A_SA); row(a.sb, dvl::A_SB);
+    row(a.res, dvl::A_RES); row(a.rpath, dvl::A_RPATH);
   }
-  c->wf_rows = arena_rows(P);
-  c->wf_paths = P;
-  c->wf_hit_cap = hit_cap;
+  c->wf_rows = A.rows;
+  c->wf_paths = L.slots;
+  c->wf_hit_cap = L.hit_cap;
   return RT_OK;
 }
 
@@ -939,7 +951,7 @@ static int apply_tiling(rt_ctx* c, int width, int height, const rt_tiling& tl, s
   dfree(c->d_cam);
   const size_t nv = std::max<size_t>(1, xy.size());
   HIPCHK(c, hipMalloc(&c->d_pix, 2 * nv * sizeof(unsigned int)));
-  HIPCHK(c, hipMalloc(&c->d_cam, 2 * nv * sizeof(float4)));
+  HIPCHK(c, hipMalloc(&c->d_cam, dvl::camera_table(xy.size(), 1).total() * sizeof(float4)));
   c->cam_sets = 1;
   if (!xy.empty()) {
     HIPCHK(c, hipMemcpy(c->d_pix, xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
@@ -1146,7 +1158,7 @@ int enter_pipelined_set(rt_ctx* c, RenderCall& call) {
   if (c->cam_sets < pipe_sets) {  // one camera table per set (a call may move the camera)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     dfree(c->d_cam);
-    HIPCHK(c, hipMalloc(&c->d_cam, 2 * (size_t)std::max(1, c->n_valid) * pipe_sets * sizeof(float4)));
+    HIPCHK(c, hipMalloc(&c->d_cam, dvl::camera_table((size_t)c->n_valid, (size_t)pipe_sets).total() * sizeof(float4)));
     c->cam_sets = pipe_sets;
     c->wf.cam = c->d_cam;
   }
@@ -1171,18 +1183,19 @@ int stage_frame_table(rt_ctx* c, const rt_frame_params* fp, int n_frames, Render
     if (T.d) HIPCHK(c, hipStreamSynchronize(c->stream));  // calls in flight read the old table
     dfree(T.d);
     const size_t cap = std::max<size_t>(call.pipe ? 16 : 1024, (size_t)n_frames);
-    HIPCHK(c, hipHostMalloc((void**)&T.h, 2 * cap * sizeof(int)));
-    // device table: [cap] loop_num, [cap] rand_origin, then [cap][4] float2 Sobol pairs and [cap]
-    // float2 blend weights (wf_sobol)
-    HIPCHK(c, hipMalloc((void**)&T.d, 12 * cap * sizeof(int)));
+    HIPCHK(c, hipHostMalloc((void**)&T.h, dvl::frame_table(cap).host_total * sizeof(int)));
+    HIPCHK(c, hipMalloc((void**)&T.d, dvl::frame_table(cap).total * sizeof(int)));
     T.cap = cap;
   }
+  const dvl::FrameTable F = dvl::frame_table(T.cap);  // (the host copy: its first two sub-tables)
+  int* const h_ro = T.h + F.rand_origin.off;
+  int* const d_ro = T.d + F.rand_origin.off;
   if (!T.ev) HIPCHK(c, hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
   HIPCHK(c, hipEventSynchronize(T.ev));  // the previous upload from this table has read T.h
   c->loop_num = call.loop_end;
   for (int k = 0; k < n_traced; k++) {
     T.h[k] = call.frames[k].loop_num;
-    T.h[T.cap + k] = call.frames[k].ro_bits;
+    h_ro[k] = call.frames[k].ro_bits;
   }
   // small calls hand the pairs to wf_sobol as kernel arguments, which writes the table
   rtd::InlineFrames IF;
@@ -1191,20 +1204,20 @@ int stage_frame_table(rt_ctx* c, const rt_frame_params* fp, int n_frames, Render
     IF.n_inline = n_traced;
     for (int k = 0; k < n_traced; k++) {
       IF.loop[k] = T.h[k];
-      memcpy(&IF.ro[k], &T.h[T.cap + k], 4);
+      memcpy(&IF.ro[k], &h_ro[k], 4);
     }
   } else if (n_traced > 0) {
     HIPCHK(c, hipMemcpyAsync(T.d, T.h, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, call.ps));
-    HIPCHK(c, hipMemcpyAsync(T.d + T.cap, T.h + T.cap, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, call.ps));
+    HIPCHK(c, hipMemcpyAsync(d_ro, h_ro, (size_t)n_traced * sizeof(int), hipMemcpyHostToDevice, call.ps));
   }
   HIPCHK(c, hipEventRecord(T.ev, call.ps));
   call.d_loop = T.d;
-  call.d_ro = reinterpret_cast<const float*>(T.d + T.cap);
-  call.d_sobol = reinterpret_cast<float2*>(T.d + 2 * T.cap);
-  call.d_blendw = reinterpret_cast<float2*>(T.d + 10 * T.cap);
+  call.d_ro = reinterpret_cast<const float*>(d_ro);
+  call.d_sobol = reinterpret_cast<float2*>(T.d + F.sobol.off);
+  call.d_blendw = reinterpret_cast<float2*>(T.d + F.blend_w.off);
   if (n_traced > 0 && wavefront) {
     hipLaunchKernelGGL(rtd::wf_sobol, dim3((4 * n_traced + 255) / 256), dim3(256), 0, call.ps, T.d,
-                       reinterpret_cast<float*>(T.d + T.cap), call.d_sobol, call.d_blendw, n_traced, IF);
+                       reinterpret_cast<float*>(d_ro), call.d_sobol, call.d_blendw, n_traced, IF);
     HIPCHK(c, hipGetLastError());
   }
   return RT_OK;
@@ -1351,9 +1364,10 @@ int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, co
     return (unsigned)((size_t)c->n_valid * g / G);
   };
   // the call's camera directions and camera hit points (WFState::org): one table of each per set
-  const size_t set_off = pipe ? (size_t)call.pset * (size_t)c->n_valid : 0;
-  plan.cam = c->wf.cam + set_off;
-  float4* const org = c->wf.cam + (size_t)c->cam_sets * (size_t)std::max(1, c->n_valid) + set_off;
+  const dvl::CameraTable CT = dvl::camera_table((size_t)c->n_valid, (size_t)c->cam_sets);
+  const size_t cam_set = pipe ? (size_t)call.pset : 0;
+  plan.cam = c->wf.cam + CT.dir(cam_set).off;
+  float4* const org = c->wf.cam + CT.org(cam_set).off;
   for (int g = 0; g < G; g++) {
     const int f0 = pix_split ? 0 : g * nf / G, f1 = pix_split ? nf : (g + 1) * nf / G;
     const unsigned int w0 = pix_split ? wbound(g) : 0u;
@@ -1514,7 +1528,7 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
       // (not when wf_finish ends the group's paths: it reads the slot-indexed state)
       bool rowc = RT_ROW_COMPACT && lean && !finish;
       if (const char* e = knob("RT_ROW_COMPACT")) rowc = rowc && atoi(e) != 0;  // (A/B)
-      size_t cap = std::min(arena_rows(slots), c->wf_rows);
+      size_t cap = std::min(dvl::arena_rows(slots), c->wf_rows);
       if (const char* e = knob("RT_ROW_CAP")) cap = std::min(cap, (size_t)strtoull(e, nullptr, 10));  // (tests: rows)
       WP.row_compact = rowc ? 1 : 0;
       WP.row_cap = (unsigned int)cap;
@@ -2142,29 +2156,23 @@ int reserve_query(rt_ctx* c, size_t rays) {
       q.mem = nullptr;
       q.cap = 0;
     }
-    const size_t n = std::max<size_t>(rays, 1024);
-    const size_t bytes = n * (16 + 8 + 4 + 8 + 24 + 48) + rtd::kCntWords * 4 + 8 * 256;  // + carve padding
-    const hipError_t me = hipMalloc(&q.mem, bytes);
-    if (me == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      q.mem = nullptr;
-      return fail(c, RT_ERR_NOMEM, "query buffers do not fit in device memory");
-    }
-    HIPCHK(c, me);
-    char* p = static_cast<char*>(q.mem);
-    auto carve = [&](size_t b) { char* r = p; p += (b + 255) & ~size_t(255); return r; };
+    const dvl::Query L = dvl::query(rays);
+    if (int rc = alloc_block(c, q.mem, L.total, "query buffers do not fit in device memory")) return rc;
     rtd::WFState& S = q.S;
     S = rtd::WFState{};
-    S.ra = S.sa = S.cam = (float4*)carve(n * 16);  // one kind of ray per chunk
-    S.rb = S.sb = (float2*)carve(n * 8);
-    S.queue[0] = S.queue_s[0] = (int*)carve(n * 4);
-    S.res = (int*)carve(n * 8);
-    q.d_in = (float*)carve(n * 24);
-    q.d_out = (float4*)carve(n * 48);
-    S.cnt = (unsigned int*)carve(rtd::kCntWords * 4);
-    q.d_zero = (float*)carve(4);
+    place(S.ra, q.mem, L.ra);  // one kind of ray per chunk
+    S.sa = S.cam = S.ra;
+    place(S.rb, q.mem, L.rb);
+    S.sb = S.rb;
+    place(S.queue[0], q.mem, L.queue);
+    S.queue_s[0] = S.queue[0];
+    place(S.res, q.mem, L.res);
+    place(q.d_in, q.mem, L.d_in);
+    place(q.d_out, q.mem, L.d_out);
+    place(S.cnt, q.mem, L.cnt);
+    place(q.d_zero, q.mem, L.zero);
     HIPCHK(c, hipMemsetAsync(q.d_zero, 0, 4, c->stream));
-    q.cap = n;
+    q.cap = L.rays;
   }
   const size_t lanes = (size_t)c->n_cus * std::max(c->trace_bpc, c->trace_bpc0) * 256;
   const size_t need = (size_t)std::max(0, std::max(c->stack_entries, c->qstack_entries) - c->trace_lds_entries) * lanes * sizeof(int2);
@@ -2455,25 +2463,13 @@ bool dn_far_lds(int s) {
 int reserve_denoise(rt_ctx* c) {
   rt_ctx::Denoise& d = c->dn;
   if (d.mem) return RT_OK;
-  const size_t npx = (size_t)c->W * c->H;
-  const size_t hit_bytes = (size_t)std::max(1, c->local_tiles) * c->tile_w * c->tile_h * sizeof(rt_hit);
-  auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t bytes = 4 * pad(npx * 16) + pad(hit_bytes) + pad(npx * 12);
-  const hipError_t me = hipMalloc(&d.mem, bytes);
-  if (me == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    d.mem = nullptr;
-    return fail(c, RT_ERR_NOMEM, "denoise buffers do not fit in device memory");
-  }
-  HIPCHK(c, me);
-  char* p = static_cast<char*>(d.mem);
-  auto carve = [&](size_t b) { char* r = p; p += pad(b); return r; };
-  d.col[0] = (float4*)carve(npx * 16);
-  d.col[1] = (float4*)carve(npx * 16);
-  d.g0 = (float4*)carve(npx * 16);
-  d.g1 = (float4*)carve(npx * 16);
-  d.hits = (float4*)carve(hit_bytes);
-  d.out = (float*)carve(npx * 12);
+  const dvl::Denoise L = dvl::denoise((size_t)c->W * c->H, (size_t)std::max(1, c->local_tiles) * c->tile_w * c->tile_h);
+  if (int rc = alloc_block(c, d.mem, L.total, "denoise buffers do not fit in device memory")) return rc;
+  for (int k = 0; k < 2; k++) place(d.col[k], d.mem, L.col[k]);
+  place(d.g0, d.mem, L.g0);
+  place(d.g1, d.mem, L.g1);
+  place(d.hits, d.mem, L.hits);
+  place(d.out, d.mem, L.out);
   d.guides = false;
   return RT_OK;
 }
@@ -2485,25 +2481,14 @@ bool dn_sigma_ok(float s) { return std::isfinite(s) && s > 0.0f; }
 int reserve_temporal(rt_ctx* c) {
   rt_ctx::Temporal& t = c->tp;
   if (t.mem) return RT_OK;
-  const size_t npx = (size_t)c->W * c->H;
-  auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t bytes = 6 * pad(npx * 16) + pad(npx * 12);
-  const hipError_t me = hipMalloc(&t.mem, bytes);
-  if (me == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    t.mem = nullptr;
-    return fail(c, RT_ERR_NOMEM, "display history does not fit in device memory");
-  }
-  HIPCHK(c, me);
-  char* p = static_cast<char*>(t.mem);
-  auto carve = [&](size_t b) { char* r = p; p += pad(b); return r; };
-  t.col[0] = (float4*)carve(npx * 16);
-  t.col[1] = (float4*)carve(npx * 16);
+  const dvl::History L = dvl::history((size_t)c->W * c->H);
+  if (int rc = alloc_block(c, t.mem, L.total, "display history does not fit in device memory")) return rc;
+  for (int k = 0; k < 2; k++) place(t.col[k], t.mem, L.col[k]);
   t.gp[0][0] = c->dn.g0;
   t.gp[0][1] = c->dn.g1;
   for (int k = 1; k < 3; k++)
-    for (int j = 0; j < 2; j++) t.gp[k][j] = (float4*)carve(npx * 16);
-  t.out = (float*)carve(npx * 12);
+    for (int j = 0; j < 2; j++) place(t.gp[k][j], t.mem, L.gp[k - 1][j]);
+  place(t.out, t.mem, L.out);
   t.drop();
   return RT_OK;
 }
@@ -2527,6 +2512,52 @@ int tp_guides_target(rt_ctx* c, bool keep_cand) {
   c->dn.g0 = t.gp[cur][0];
   c->dn.g1 = t.gp[cur][1];
   return cur;
+}
+
+// The state a display stage (rt_denoise_async, rt_temporal_async) needs, checked after its own
+// arguments: a scene and a frame, one rank, guides to reuse, a camera where one is read
+int display_state(rt_ctx* c, const rt_frame_params* fp, bool reuse, bool camera, const char* no_guides) {
+  if (!c->scene_set || !c->frame_set) return fail(c, RT_ERR_STATE, "rt_set_scene and rt_resize first");
+  if (c->world != 1) return fail(c, RT_ERR_STATE, "a multi-rank context has guides for its own pixels only");
+  if (reuse && !(c->dn.mem && c->dn.guides)) return fail(c, RT_ERR_STATE, no_guides);
+  if (camera)
+    if (int rc = camera_args(c, fp, true)) return rc;
+  return RT_OK;
+}
+
+// A display stage's input, after its reserve: the frame's colour in dn.col[0] and the current
+// guides in dn.g0 / dn.g1 = guide pair `pair` (a fresh pack's: tp_guides_target), from the caller's
+// hits or the library's own first-hit trace.
+// The pack reads the accumulation on the ctx stream, after the render calls queued before it
+// (the stream joins each of them); a render call queued afterwards blends only after it, as
+// after rt_tonemap_async's pass (a pipelined call's blend waits for the ctx stream at its entry).
+int display_pack(rt_ctx* c, const rt_frame_params* fp, bool reuse, const float* frame_in_device, const void* hits_dev,
+                 bool keep_cand, int& pair) {
+  rt_ctx::Denoise& d = c->dn;
+  pair = reuse ? tp_current_pair(c) : tp_guides_target(c, keep_cand);
+  if (!reuse && !hits_dev) {
+    d.guides = false;  // (they are being replaced: a failure below leaves none)
+    if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
+  }
+  const dim3 pgrid((c->W + 255) / 256, c->H);
+  const float4* tiles = frame_in_device ? nullptr : c->d_accum;
+  if (reuse)
+    hipLaunchKernelGGL(rtd::dn_pack<false>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device, (const float4*)nullptr,
+                       d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w, c->tile_h, c->tiles_x);
+  else
+    hipLaunchKernelGGL(rtd::dn_pack<true>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device,
+                       hits_dev ? (const float4*)hits_dev : d.hits, d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w,
+                       c->tile_h, c->tiles_x);
+  HIPCHK(c, hipGetLastError());
+  d.guides = true;
+  return RT_OK;
+}
+
+// The blocking forms' tail: the stage's output frame (W*H*3 floats) to the host
+int display_fetch(rt_ctx* c, const float* out, float* rgb_out_host) {
+  HIPCHK(c, hipMemcpyAsync(rgb_out_host, out, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
 }
 
 }  // namespace
@@ -2554,33 +2585,12 @@ int rt_denoise_async(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_para
   const bool reuse = (dp->flags & RT_DENOISE_REUSE_GUIDES) != 0;
   const bool trace = !reuse && !hits_dev;
   if (trace && !fp) return fail(c, RT_ERR_ARG, "null frame parameters");
-  if (!c->scene_set || !c->frame_set) return fail(c, RT_ERR_STATE, "rt_set_scene and rt_resize first");
-  if (c->world != 1) return fail(c, RT_ERR_STATE, "a multi-rank context has guides for its own pixels only");
-  if (reuse && !(c->dn.mem && c->dn.guides)) return fail(c, RT_ERR_STATE, "no guides of an earlier denoise call for this size");
-  if (trace)
-    if (int rc = camera_args(c, fp, true)) return rc;
+  if (int rc = display_state(c, fp, reuse, trace, "no guides of an earlier denoise call for this size")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = reserve_denoise(c)) return rc;
   rt_ctx::Denoise& d = c->dn;
-  if (!reuse) tp_guides_target(c, true);
-  if (trace) {
-    d.guides = false;  // (they are being replaced: a failure below leaves none)
-    if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
-  }
-  // The pack reads the accumulation on the ctx stream, after the render calls queued before it
-  // (the stream joins each of them); a render call queued afterwards blends only after it, as
-  // after rt_tonemap_async's pass (a pipelined call's blend waits for the ctx stream at its entry).
-  const dim3 pgrid((c->W + 255) / 256, c->H);
-  const float4* tiles = frame_in_device ? nullptr : c->d_accum;
-  if (reuse)
-    hipLaunchKernelGGL(rtd::dn_pack<false>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device, (const float4*)nullptr,
-                       d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w, c->tile_h, c->tiles_x);
-  else
-    hipLaunchKernelGGL(rtd::dn_pack<true>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device,
-                       hits_dev ? (const float4*)hits_dev : d.hits, d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w,
-                       c->tile_h, c->tiles_x);
-  HIPCHK(c, hipGetLastError());
-  d.guides = true;
+  int pair;  // (a live candidate of the display history keeps its guides)
+  if (int rc = display_pack(c, fp, reuse, frame_in_device, hits_dev, true, pair)) return rc;
   rtd::DnIter I;
   I.g0 = d.g0;
   I.g1 = d.g1;
@@ -2620,9 +2630,7 @@ int rt_denoise(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_params* dp
   if (!rgb_out_host) return fail(c, RT_ERR_ARG, "null output");
   float* out = nullptr;
   if (int rc = rt_denoise_async(c, fp, dp, nullptr, nullptr, &out)) return rc;
-  HIPCHK(c, hipMemcpyAsync(rgb_out_host, out, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return display_fetch(c, out, rgb_out_host);
 }
 
 // ----------------------------------------------------------------------------- display history
@@ -2646,11 +2654,7 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
   if (!dn_sigma_ok(tp->sigma_normal) || !dn_sigma_ok(tp->sigma_plane)) return fail(c, RT_ERR_ARG, "a sigma is not finite and > 0");
   if (tp->flags & ~(RT_TEMPORAL_ADVANCE | RT_TEMPORAL_REUSE_GUIDES | RT_TEMPORAL_RESET)) return fail(c, RT_ERR_ARG, "unknown flags");
   const bool reuse = (tp->flags & RT_TEMPORAL_REUSE_GUIDES) != 0;
-  const bool trace = !reuse && !hits_dev;
-  if (!c->scene_set || !c->frame_set) return fail(c, RT_ERR_STATE, "rt_set_scene and rt_resize first");
-  if (c->world != 1) return fail(c, RT_ERR_STATE, "a multi-rank context has guides for its own pixels only");
-  if (reuse && !(c->dn.mem && c->dn.guides)) return fail(c, RT_ERR_STATE, "no guides of an earlier denoise or temporal call for this size");
-  if (int rc = camera_args(c, fp, true)) return rc;
+  if (int rc = display_state(c, fp, reuse, true, "no guides of an earlier denoise or temporal call for this size")) return rc;
   for (int a = 0; a < 3; a++)
     if (!std::isfinite(fp->front[a])) return fail(c, RT_ERR_ARG, "non-finite camera");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2667,23 +2671,8 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
     t.hist_fp = t.cand_fp;
   }
   t.cand = t.cand_g = -1;
-  const int pair = reuse ? tp_current_pair(c) : tp_guides_target(c, false);  // (the old candidate's is free)
-  if (trace) {
-    d.guides = false;  // (they are being replaced: a failure below leaves none)
-    if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
-  }
-  // The pack reads the accumulation on the ctx stream: ordering as in rt_denoise_async
-  const dim3 pgrid((c->W + 255) / 256, c->H);
-  const float4* tiles = frame_in_device ? nullptr : c->d_accum;
-  if (reuse)
-    hipLaunchKernelGGL(rtd::dn_pack<false>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device, (const float4*)nullptr,
-                       d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w, c->tile_h, c->tiles_x);
-  else
-    hipLaunchKernelGGL(rtd::dn_pack<true>, pgrid, dim3(256), 0, c->stream, tiles, frame_in_device,
-                       hits_dev ? (const float4*)hits_dev : d.hits, d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w,
-                       c->tile_h, c->tiles_x);
-  HIPCHK(c, hipGetLastError());
-  d.guides = true;
+  int pair;  // (the old candidate's is free)
+  if (int rc = display_pack(c, fp, reuse, frame_in_device, hits_dev, false, pair)) return rc;
   const int cand = t.hist == 0 ? 1 : 0;
   rtd::TpCall T;
   T.cur = d.col[0];
@@ -2720,9 +2709,7 @@ int rt_temporal(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_params* 
   if (!rgb_out_host) return fail(c, RT_ERR_ARG, "null output");
   float* out = nullptr;
   if (int rc = rt_temporal_async(c, fp, tp, nullptr, nullptr, &out)) return rc;
-  HIPCHK(c, hipMemcpyAsync(rgb_out_host, out, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return display_fetch(c, out, rgb_out_host);
 }
 
 int rt_temporal_history(rt_ctx* c, float* n_out_host) {

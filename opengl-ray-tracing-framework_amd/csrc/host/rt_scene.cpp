@@ -7,6 +7,7 @@
 // reproduces the reference's BVH node arrays bit for bit.  Compiled with
 // -ffp-contract=off (no FMA contraction, as the reference's x86-64 SSE build).
 #include "rt_scene.h"
+#include "dev_layout.h"
 #include "scene_compile.h"
 #include "tri_filter.h"
 
@@ -1301,6 +1302,76 @@ int rts_tri_filter(const float* tri, int n_triangles, float* out, double* k, int
   k[1] = c.k0;
   if (flagged) *flagged = c.flagged;
   return 0;
+}
+
+int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_dev_span* spans, int32_t cap,
+                   int32_t* n_spans) {
+  if (!scalars || !spans || !n_spans || cap < 0) return RTS_ERR_ARG;
+  int32_t k = 0;
+  bool fits = true;
+  // span k: `at` moved by `base`; host = the span it lies in (-1: memory of its own)
+  auto put = [&](dvl::Span at, size_t base, int32_t host, bool live) {
+    if (k < cap) spans[k] = rts_dev_span{base + at.off, at.bytes, host, live ? 1 : 0};
+    else fits = false;
+    return k++;
+  };
+  for (int i = 0; i < 8; i++) scalars[i] = 0;
+  switch (kind) {
+    case RTS_LAYOUT_PATH_STATE: {
+      if (m < 1 || m > 4) return RTS_ERR_ARG;
+      const dvl::PathState L = dvl::path_state(n, (int)m);
+      const dvl::Arena A = dvl::arena(L);
+      const uint64_t s[8] = {L.total, L.set_bytes, L.slots, L.hit_cap, A.rows, dvl::slot_bytes(), dvl::row_bytes(), 0};
+      std::copy(s, s + 8, scalars);
+      for (int g = 0; g < (int)m; g++) {
+        const size_t set = L.set(g);
+        const int32_t first = k;
+        for (int i = 0; i < dvl::kSlotArrays; i++) put(L.arr[i], set, -1, dvl::kSlot[i].lean_live);
+        for (int q = 0; q < 2; q++) put(L.queue_s[q], set, first + dvl::QUEUE0 + q, true);
+        put(L.hit, set, -1, true);
+        put(L.cnt, set, -1, true);
+        for (int i = 0; i < dvl::kArenaArrays; i++) put(A.arr[i], set, first + dvl::kArena[i].host, false);
+      }
+      break;
+    }
+    case RTS_LAYOUT_QUERY: {
+      const dvl::Query L = dvl::query(n);
+      scalars[0] = L.total;
+      scalars[1] = L.rays;
+      for (dvl::Span at : {L.ra, L.rb, L.queue, L.res, L.d_in, L.d_out, L.cnt, L.zero}) put(at, 0, -1, true);
+      break;
+    }
+    case RTS_LAYOUT_DENOISE: {
+      const dvl::Denoise L = dvl::denoise(n, m);
+      scalars[0] = L.total;
+      for (dvl::Span at : {L.col[0], L.col[1], L.g0, L.g1, L.hits, L.out}) put(at, 0, -1, true);
+      break;
+    }
+    case RTS_LAYOUT_HISTORY: {
+      const dvl::History L = dvl::history(n);
+      scalars[0] = L.total;
+      for (dvl::Span at : {L.col[0], L.col[1], L.gp[0][0], L.gp[0][1], L.gp[1][0], L.gp[1][1], L.out}) put(at, 0, -1, true);
+      break;
+    }
+    case RTS_LAYOUT_FRAME_TABLE: {
+      const dvl::FrameTable L = dvl::frame_table(n);
+      scalars[0] = L.total;
+      scalars[1] = L.host_total;
+      for (dvl::Span at : {L.loop_num, L.rand_origin, L.sobol, L.blend_w}) put(at, 0, -1, true);
+      break;
+    }
+    case RTS_LAYOUT_CAMERA_TABLE: {
+      if (m > 8) return RTS_ERR_ARG;
+      const dvl::CameraTable L = dvl::camera_table(n, m);
+      scalars[0] = L.total();
+      for (size_t p = 0; p < m; p++) put(L.dir(p), 0, -1, true);
+      for (size_t p = 0; p < m; p++) put(L.org(p), 0, -1, true);
+      break;
+    }
+    default: return RTS_ERR_ARG;
+  }
+  *n_spans = k;
+  return fits ? RTS_OK : RTS_ERR_ARG;
 }
 
 // ---- the HIP path's scene compiler (csrc/common/scene_compile.h), for tests and tooling

@@ -139,6 +139,7 @@ def lib() -> C.CDLL:
         L.rts_glibc_rand.argtypes = [C.c_uint, C.c_int, C.POINTER(C.c_int)]
         L.rts_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
         L.rts_tri_filter.argtypes = [_f32p, C.c_int, _f32p, C.POINTER(C.c_double), _i32p]
+        L.rts_dev_layout.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_int32, _i32p]
         L.rts_compile_scene.argtypes = [vp, _i32p, C.POINTER(vp)]
         L.rts_compile_scene_encoded.argtypes = [_f32p, C.c_int32, _f32p, C.c_int32, _i32p, C.POINTER(vp)]
         L.rts_compiled_get.argtypes = [vp, C.POINTER(RtsCompiledView)]
@@ -356,6 +357,46 @@ def tri_filter(tri: np.ndarray):
     fl = np.zeros(1, np.int32)
     _check(lib().rts_tri_filter(_fp(tri), n, _fp(out), k, _ip(fl)), "rts_tri_filter")
     return out, float(k[0]), float(k[1]), int(fl[0])
+
+
+# rts_dev_layout's kinds and the names of their spans (one set's, for the path state), in order
+LAYOUT_KINDS = ("path_state", "query", "denoise", "history", "frame_table", "camera_table")
+_SLOT_NAMES = ("s0", "s1", "s2", "s3", "s4", "s5", "ra", "rb", "sa", "sb", "res", "fin", "queue0", "queue1",
+               "active0", "active1", "queue_s0", "queue_s1", "hit", "cnt")
+_ROW_NAMES = ("s0", "s1", "s2", "s3", "s4", "s5", "ra", "rb", "sa", "sb", "res", "rpath")
+LAYOUT_SPANS = {
+    "path_state": _SLOT_NAMES + tuple("arena." + r for r in _ROW_NAMES),
+    "query": ("ra", "rb", "queue", "res", "d_in", "d_out", "cnt", "zero"),
+    "denoise": ("col0", "col1", "g0", "g1", "hits", "out"),
+    "history": ("col0", "col1", "gp1.g0", "gp1.g1", "gp2.g0", "gp2.g1", "out"),
+    "frame_table": ("loop_num", "rand_origin", "sobol", "blend_w"),
+}
+
+
+class RtsDevSpan(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("bytes", C.c_uint64), ("host", C.c_int32), ("live", C.c_int32)]
+
+
+def dev_layout(kind: str, n: int, m: int = 1):
+    """A carved device allocation of the HIP path (csrc/common/dev_layout.h) for sizes n, m:
+    (scalars, spans), the 8 scalars of rts_dev_layout (rt_scene.h; the total first) and its spans
+    as dicts {name, off, bytes, host, live}.  Units are bytes, ints in the frame table and float4
+    in the camera table; host is the index of the span this one lies in, or -1.  Path-state names
+    carry their set ("1.s0", "1.arena.s0"), camera-table names are "dir<p>" and "org<p>"."""
+    cap = 256
+    scalars = (C.c_uint64 * 8)()
+    spans = (RtsDevSpan * cap)()
+    cnt = C.c_int32()
+    _check(lib().rts_dev_layout(LAYOUT_KINDS.index(kind), n, m, scalars, spans, cap, C.byref(cnt)), "rts_dev_layout")
+    if kind == "path_state":
+        names = [f"{g}.{s}" for g in range(m) for s in LAYOUT_SPANS[kind]]
+    elif kind == "camera_table":
+        names = [f"{t}{p}" for t in ("dir", "org") for p in range(m)]
+    else:
+        names = list(LAYOUT_SPANS[kind])
+    assert len(names) == cnt.value, (kind, len(names), cnt.value)
+    return list(scalars), [dict(name=nm, off=s.off, bytes=s.bytes, host=s.host, live=s.live)
+                           for nm, s in zip(names, spans)]
 
 
 @dataclasses.dataclass
