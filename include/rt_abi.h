@@ -175,6 +175,45 @@ int rt_set_scene(rt_ctx* ctx, const rt_scene_soa* scene);
 int rt_set_scene_encoded(rt_ctx* ctx, const float* tri_enc, int32_t n_triangles, const float* node_enc,
                          int32_t n_nodes);
 int rt_update_materials(rt_ctx* ctx, int32_t first, int32_t count, const rt_material* material);
+/* ---- Geometry update (RT_HAS_GEOMETRY_UPDATE, an addition within ABI 7: find it by symbol) -----------
+ * New vertices for triangles of the scene set by rt_set_scene; the topology (triangle count and order,
+ * leaves, both trees' structure, materials) stays.  Triangle t = first + i when tri_index is NULL, else
+ * tri_index[i] (then first must be 0); p1..n3 hold 3 floats per updated triangle.  Everything derived
+ * from the vertices is recomputed on the device (the geometric normals, the traversal records and their
+ * edge filter, the shade's hit records) and every box of both trees is refitted as the exact min / max
+ * union of what lies below it, so renders and queries return what a fresh rt_set_scene of the moved
+ * triangles over the same tree returns, bit for bit.  The culling bound and the edge filter's margin only
+ * grow under updates (more fallbacks to the reference's own test, never another answer); the tree is
+ * not rebuilt for the new pose (rt_set_scene remains the way to a tree built for it).
+ *   Like rt_update_materials, both calls wait for the render calls in flight, work on the context's
+ * stream and return when the update is complete.  They leave LoopNum, the accumulation, rt_stats,
+ * rt_order_work's order, the materials and the temporal history as they were (the caller resets what it
+ * wants reset) and forget the current denoise / temporal guides: RT_DENOISE_REUSE_GUIDES and
+ * RT_TEMPORAL_REUSE_GUIDES return RT_ERR_STATE until a call packs fresh ones.  Every rank of a
+ * multi-rank job makes the same call (each rank holds the whole scene).
+ *   RT_ERR_STATE before rt_set_scene.  RT_ERR_ARG, with the scene untouched: count < 0, a null array with
+ * count > 0, first != 0 with an index list, an index or range outside the triangle list, a duplicate
+ * index (host form), a non-finite position or normal, |position| >= 2^30.  count == 0: RT_OK.
+ *   rt_update_geometry_device takes device pointers (vertices produced on the GPU): it checks ranges and
+ * values in a kernel that reads only its inputs, but cannot see duplicates: distinct indices are the
+ * caller's contract there (a duplicate leaves one of the two triangles' data, never an invalid access).
+ * The arrays must be complete on the context's stream, or the caller synchronises first.
+ *   rt_scene_download copies one device array as it stands (bytes must be its size: 48 per triangle for
+ * TRI / TRX / TRIN with at least one triangle's worth for TRX, 128 per triangle for HREC, 64 per binary
+ * node, 128 per 4-wide node); rt_scene_bounds returns the scene's margins {cull_R, cull_K, cull_off,
+ * tri_k1, tri_k0} and the number of triangles the edge filter leaves to the reference's test.  Both are
+ * for tests and tooling.  Out of scope: topology changes, shrinking the margins, reprojecting a moving
+ * surface's display history, an asynchronous update. */
+#define RT_HAS_GEOMETRY_UPDATE 1
+int rt_update_geometry(rt_ctx* ctx, const int32_t* tri_index, int32_t first, int32_t count, const float* p1,
+                       const float* p2, const float* p3, const float* n1, const float* n2, const float* n3);
+int rt_update_geometry_device(rt_ctx* ctx, const void* tri_index_dev, int32_t first, int32_t count, const void* p1_dev,
+                              const void* p2_dev, const void* p3_dev, const void* n1_dev, const void* n2_dev,
+                              const void* n3_dev);
+enum { RT_SCENE_TRI = 0, RT_SCENE_TRX, RT_SCENE_TRIN, RT_SCENE_HREC, RT_SCENE_NODES, RT_SCENE_QNODES };
+int rt_scene_download(rt_ctx* ctx, int32_t which, void* out, size_t bytes);
+int rt_scene_array_bytes(rt_ctx* ctx, int32_t which, size_t* bytes);   /* the size rt_scene_download expects */
+int rt_scene_bounds(rt_ctx* ctx, double out[5], int32_t* tri_flagged);
 /* hdr_rgb / cache_rgb: w*h*3 floats, row 0 = first uploaded row (texture v = 0). */
 int rt_set_env(rt_ctx* ctx, const float* hdr_rgb, const float* cache_rgb, int32_t w, int32_t h,
                int32_t hdr_resolution);
@@ -441,7 +480,8 @@ int rt_denoise(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_params* 
  * (n H + k acc_k) / (n + k) against a frozen H.  Pass ADVANCE on the first display after the
  * accumulation restarted.  RT_TEMPORAL_RESET drops history and candidate before the call;
  * rt_resize and rt_set_scene drop them too.
- * Out of scope: motion of scene objects, view-dependent (specular) reprojection, variance
+ * Out of scope: reprojecting the history of a surface rt_update_geometry moved (the caller resets it:
+ * RT_TEMPORAL_RESET), view-dependent (specular) reprojection, variance
  * estimation, multi-rank contexts (RT_ERR_STATE when world != 1). */
 #define RT_HAS_TEMPORAL 1
 typedef struct rt_temporal_params {

@@ -178,6 +178,31 @@ int rts_compile_scene_encoded(const float* tri_enc, int32_t n_triangles, const f
 int rts_compiled_get(const rts_compiled* k, rts_compiled_view* view);
 void rts_compiled_free(rts_compiled* k);
 
+/* Geometry update of a compiled scene (scn::update_geometry, the definition rt_update_geometry
+ * follows on the device): new vertices for `count` triangles, t = first + i when tri_index is NULL,
+ * else tri_index[i] (then first must be 0, and the indices distinct).  p1..n3 are float[3 * count].
+ * tri, trin.xyz, hrec and trx are recomputed (the edge filter's caps stay those of the compile), the
+ * culling bound and the filter's margin only grow, and every box of both trees is refitted over
+ * the unchanged topology.  Returns rt_update_geometry's code: RT_OK, or RT_ERR_ARG (a null array
+ * with count > 0, count < 0, an index outside the triangle list, a duplicate index, a non-finite
+ * value, |position| >= 2^30) with the handle unchanged and the reason in the view's err. */
+int rts_compiled_update_geometry(rts_compiled* k, const int32_t* tri_index, int32_t first, int32_t count,
+                                 const float* p1, const float* p2, const float* p3, const float* n1, const float* n2,
+                                 const float* n3);
+/* The edge filter's state: out = {s_cap, sc_cap, s_max, sc_max, c_min} (tri_filter.h: the caps of
+ * the compile and the extrema tri_k1 / tri_k0 are formed from). */
+int rts_compiled_filter_state(const rts_compiled* k, double out[5]);
+/* The device's refit schedule (scn::refit_plan), for tests: leaves = 4 int32 per leaf {ref, binary
+ * parent * 2 + side, 4-wide parent * 4 + slot, 0} (-1: the root is that leaf / no 4-wide tree);
+ * blist / qlist = the internal nodes of the binary / 4-wide tree ordered by height (a leaf is 0, a
+ * node 1 + the highest of its children): height h is list[off[h - 1] .. off[h]), off[0] = 0.  The
+ * pointers live until the next call for the handle. */
+typedef struct rts_refit_plan_view {
+  const int32_t *leaves, *blist, *boff, *qlist, *qoff;
+  int32_t n_leaves, n_blist, n_boff, n_qlist, n_qoff;
+} rts_refit_plan_view;
+int rts_refit_plan(rts_compiled* k, rts_refit_plan_view* view);
+
 /* 8-bit RGB PNG (stbi_write_png in SaveFrame, src/core/Utility.h:19-30): width*height*3 bytes,
  * row 0 = top (rt_tonemap's output order).  Stored (uncompressed) deflate, no zlib needed. */
 int rts_write_png(const char* path, int width, int height, const uint8_t* rgb);

@@ -24,6 +24,8 @@
 
 namespace scn {
 
+#define SCN_HD TRIF_HD
+
 // Child references of both trees: an internal node's index, or a leaf's triangle range
 // (LEAF_BIT | first << 4 | count - 1, at most 16 triangles); Q_EMPTY marks an empty 4-wide slot.
 constexpr int Q_EMPTY = 0x7fffffff;
@@ -67,10 +69,14 @@ struct Compiled {
   double cull_R = 0.0, cull_K = 0.0, cull_off = 0.0;  // culling bound of the scene (cull_bound_stats)
   double tri_k1 = 0.0, tri_k0 = 0.0;                  // the edge filter's margin
   int tri_flagged = 0;
+  // the edge filter's state (trif::Consts): the caps of the last compile and the extrema k1, k0 are
+  // formed from; update_geometry keeps the caps and lets the extrema grow
+  double s_cap = 0.0, sc_cap = 0.0, s_max = 0.0, sc_max = 0.0, c_min = 1.0;
+  bool qbuilt = false;  // qnodes / qroot describe a 4-wide tree (build_wide did not give up)
 };
 
 // Same fp32 operations as the shader's per-test N = normalize(cross(p2-p1, p3-p1)) (RT:253).
-inline void geometric_normal(const float* p1, const float* p2, const float* p3, float* n) {
+SCN_HD inline void geometric_normal(const float* p1, const float* p2, const float* p3, float* n) {
   float ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
   float bx = p3[0] - p1[0], by = p3[1] - p1[1], bz = p3[2] - p1[2];
   float cx = ay * bz - by * az, cy = az * bx - bz * ax, cz = ax * by - bx * ay;
@@ -92,31 +98,40 @@ inline void geometric_normal(const float* p1, const float* p2, const float* p3, 
 struct CullStats {
   double R = 0.0, K = 0.0, off = 0.0;
 };
+// One triangle's contribution; the scene's three values are the maxima over its triangles.
+SCN_HD inline CullStats cull_tri(const float* p1, const float* p2, const float* p3) {
+  CullStats cs;
+  const float* p[3] = {p1, p2, p3};
+  float ng[3];
+  geometric_normal(p[0], p[1], p[2], ng);
+  for (int k = 0; k < 3; k++)
+    for (int a = 0; a < 3; a++) cs.R = trif::dmax_(cs.R, fabs((double)p[k][a]));
+  if (!(trif::finitef_(ng[0]) && trif::finitef_(ng[1]) && trif::finitef_(ng[2]))) return cs;  // never hit (NaN tests)
+  double e1[3], e2[3], cx[3];
+  for (int a = 0; a < 3; a++) { e1[a] = (double)p[1][a] - p[0][a]; e2[a] = (double)p[2][a] - p[0][a]; }
+  cx[0] = e1[1] * e2[2] - e1[2] * e2[1];
+  cx[1] = e1[2] * e2[0] - e1[0] * e2[2];
+  cx[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  const double nrm = sqrt(cx[0] * cx[0] + cx[1] * cx[1] + cx[2] * cx[2]);
+  const double cosT = nrm > 0.0 ? (ng[0] * cx[0] + ng[1] * cx[1] + ng[2] * cx[2]) / nrm : 0.0;
+  if (!(cosT > 0.25)) { cs.K = (double)INFINITY; return cs; }
+  cs.K = 44.0 + 70.0 / cosT;
+  for (int k = 1; k < 3; k++) {
+    double o = 0.0;
+    for (int a = 0; a < 3; a++) o += ((double)p[k][a] - p[0][a]) * ng[a];
+    cs.off = trif::dmax_(cs.off, fabs(o));
+  }
+  return cs;
+}
+inline void cull_merge(CullStats& cs, const CullStats& t) {
+  cs.R = std::max(cs.R, t.R);
+  cs.K = std::max(cs.K, t.K);
+  cs.off = std::max(cs.off, t.off);
+}
 inline CullStats cull_bound_stats(const rt_scene_soa* s) {
   CullStats cs;
   const int nt = s->n_triangles;
-  for (int i = 0; i < nt; i++) {
-    const float* p[3] = {s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i};
-    float ng[3];
-    geometric_normal(p[0], p[1], p[2], ng);
-    for (int k = 0; k < 3; k++)
-      for (int a = 0; a < 3; a++) cs.R = std::max(cs.R, std::fabs((double)p[k][a]));
-    if (!(std::isfinite(ng[0]) && std::isfinite(ng[1]) && std::isfinite(ng[2]))) continue;  // never hit (NaN tests)
-    double e1[3], e2[3], cx[3];
-    for (int a = 0; a < 3; a++) { e1[a] = (double)p[1][a] - p[0][a]; e2[a] = (double)p[2][a] - p[0][a]; }
-    cx[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    cx[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    cx[2] = e1[0] * e2[1] - e1[1] * e2[0];
-    const double nrm = std::sqrt(cx[0] * cx[0] + cx[1] * cx[1] + cx[2] * cx[2]);
-    const double cosT = nrm > 0.0 ? (ng[0] * cx[0] + ng[1] * cx[1] + ng[2] * cx[2]) / nrm : 0.0;
-    if (!(cosT > 0.25)) { cs.K = INFINITY; continue; }
-    cs.K = std::max(cs.K, 44.0 + 70.0 / cosT);
-    for (int k = 1; k < 3; k++) {
-      double o = 0.0;
-      for (int a = 0; a < 3; a++) o += ((double)p[k][a] - p[0][a]) * ng[a];
-      cs.off = std::max(cs.off, std::fabs(o));
-    }
-  }
+  for (int i = 0; i < nt; i++) cull_merge(cs, cull_tri(s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i));
   // every leaf's triangles inside the leaf's box (the reference's own boxes are their min/max)
   for (int n = 1; n < s->n_nodes && s->node_n; n++) {
     if (s->node_n[n] <= 0) continue;
@@ -409,6 +424,26 @@ inline bool build_wide(const Options& opt, std::vector<BNode>& gn, int root, std
   return true;
 }
 
+// One triangle's tri texels {p_k, Ng[k]} and the xyz of its trin texels (every .w stays: material
+// id, leaf rank, 0).  compile() and the geometry update (host model and device) run this.
+SCN_HD inline void tri_record(const float* p1, const float* p2, const float* p3, const float* n1, const float* n2,
+                              const float* n3, float* tri, float* trin) {
+  float ng[3];
+  geometric_normal(p1, p2, p3, ng);
+  const float* ps[3] = {p1, p2, p3};
+  const float* ns[3] = {n1, n2, n3};
+  for (int k = 0; k < 3; k++) {
+    float* t = tri + 4 * k;
+    float* n = trin + 4 * k;
+    t[0] = ps[k][0]; t[1] = ps[k][1]; t[2] = ps[k][2]; t[3] = ng[k];
+    n[0] = ns[k][0]; n[1] = ns[k][1]; n[2] = ns[k][2];
+  }
+}
+// The shade's hit record of one triangle: tri's three texels then trin's (floats 24..31 unused)
+SCN_HD inline void hit_record(const float* tri, const float* trin, float* hrec) {
+  for (int j = 0; j < 12; j++) { hrec[j] = tri[j]; hrec[12 + j] = trin[j]; }
+}
+
 // rt_scene_soa -> Compiled.  Returns RT_OK, or RT_ERR_ARG / RT_ERR_LIMIT with the reason in `err`
 // and `out` untouched.
 inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std::string& err) {
@@ -431,18 +466,11 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
   c.tri.resize(12 * (size_t)nt);
   c.trin.resize(12 * (size_t)nt);
   for (int i = 0; i < nt; i++) {
-    float ng[3];
-    geometric_normal(s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i, ng);
-    const float* ps[3] = {s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i};
-    const float* ns[3] = {s->n1 + 3 * i, s->n2 + 3 * i, s->n3 + 3 * i};
-    for (int k = 0; k < 3; k++) {
-      float* t = &c.tri[4 * (3 * (size_t)i + k)];
-      float* n = &c.trin[4 * (3 * (size_t)i + k)];
-      t[0] = ps[k][0]; t[1] = ps[k][1]; t[2] = ps[k][2]; t[3] = ng[k];
-      float w = 0.0f;
-      if (k == 0) memcpy(&w, &s->material_id[i], 4);
-      n[0] = ns[k][0]; n[1] = ns[k][1]; n[2] = ns[k][2]; n[3] = w;
-    }
+    float* n = &c.trin[12 * (size_t)i];
+    n[3] = n[7] = n[11] = 0.0f;
+    memcpy(&n[3], &s->material_id[i], 4);
+    tri_record(s->p1 + 3 * i, s->p2 + 3 * i, s->p3 + 3 * i, s->n1 + 3 * i, s->n2 + 3 * i, s->n3 + 3 * i,
+               &c.tri[12 * (size_t)i], n);
   }
   // ---- materials
   c.mats.assign(32 * (size_t)std::max(1, s->n_materials), 0.0f);
@@ -503,7 +531,7 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
     c.has_scene = 1;
   }
   c.qroot = c.root;
-  if (c.has_scene) c.wide = build_wide(opt, c.nodes, c.root, c.trin, c.qnodes, c.qroot, c.qdepth);
+  if (c.has_scene) c.wide = c.qbuilt = build_wide(opt, c.nodes, c.root, c.trin, c.qnodes, c.qroot, c.qdepth);
   if (!opt.wide) c.wide = false;
   if (c.nodes.empty()) c.nodes.push_back(BNode{});
   if (c.qnodes.empty()) c.qnodes.push_back(WNode{});
@@ -511,19 +539,221 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
     c.trx.assign(std::max<size_t>(12, c.tri.size()), 0.0f);
     const trif::Consts k = trif::build(c.tri.data(), nt, c.trx.data());
     c.tri_k1 = k.k1; c.tri_k0 = k.k0; c.tri_flagged = k.flagged;
+    c.s_cap = k.s_cap; c.sc_cap = k.sc_cap; c.s_max = k.s_max; c.sc_max = k.sc_max; c.c_min = k.c_min;
   }
   // hit records: tri's three texels then trin's, one 128-B line per triangle
   c.hrec.assign(32 * std::max<size_t>(1, (size_t)nt), 0.0f);
-  for (size_t i = 0; i < (size_t)nt; i++) {
-    memcpy(&c.hrec[32 * i], &c.tri[12 * i], 48);
-    memcpy(&c.hrec[32 * i + 12], &c.trin[12 * i], 48);
-  }
+  for (size_t i = 0; i < (size_t)nt; i++) hit_record(&c.tri[12 * i], &c.trin[12 * i], &c.hrec[32 * i]);
   {
     const CullStats cs = cull_bound_stats(s);
     c.cull_R = cs.R; c.cull_K = cs.K; c.cull_off = cs.off;
   }
   out = std::move(c);
   return RT_OK;
+}
+
+// ---- Geometry update: new vertices for some triangles, topology kept ----------
+// glm's min / max: the definitions fix which zero a tie between -0 and +0 returns, the same in
+// this model, in the device kernels and in the tests.
+SCN_HD inline float gmin(float a, float b) { return (b < a) ? b : a; }
+SCN_HD inline float gmax(float a, float b) { return (a < b) ? b : a; }
+
+// A leaf's box, the reference's (BVH.h:116-134): from +-1145141919 over its triangles in ascending
+// index, per axis the min / max of the three vertices first.  tri: the device layout (12 floats
+// per triangle).
+SCN_HD inline void leaf_box(const float* tri, int ref, float* lo, float* hi) {
+  for (int a = 0; a < 3; a++) { lo[a] = 1145141919.0f; hi[a] = -1145141919.0f; }
+  const int first = leaf_first(ref), n = leaf_count(ref);
+  for (int t = first; t < first + n; t++) {
+    const float* p = tri + 12 * (size_t)t;
+    for (int a = 0; a < 3; a++) {
+      lo[a] = gmin(lo[a], gmin(p[a], gmin(p[4 + a], p[8 + a])));
+      hi[a] = gmax(hi[a], gmax(p[a], gmax(p[4 + a], p[8 + a])));
+    }
+  }
+}
+// Box of a binary node: its left child box, then its right one
+SCN_HD inline void bnode_box(const BNode& g, float* lo, float* hi) {
+  for (int a = 0; a < 3; a++) { lo[a] = gmin(g.box[a], g.box[6 + a]); hi[a] = gmax(g.box[3 + a], g.box[9 + a]); }
+}
+// Box of a 4-wide node: its non-empty slots in slot order (slot 0 is never empty)
+SCN_HD inline void wnode_box(const WNode& q, float* lo, float* hi) {
+  for (int a = 0; a < 3; a++) { lo[a] = q.lo[a][0]; hi[a] = q.hi[a][0]; }
+  for (int i = 1; i < 4; i++) {
+    if (q.ref[i] == Q_EMPTY) continue;
+    for (int a = 0; a < 3; a++) { lo[a] = gmin(lo[a], q.lo[a][i]); hi[a] = gmax(hi[a], q.hi[a][i]); }
+  }
+}
+
+// Every box of both trees from the triangles as they stand.
+inline void refit(Compiled& c) {
+  if (!c.has_scene) return;
+  const float* tri = c.tri.data();
+  std::function<void(int, float*, float*)> rb = [&](int ref, float* lo, float* hi) {
+    if (ref_is_leaf(ref)) { leaf_box(tri, ref, lo, hi); return; }
+    BNode& g = c.nodes[ref];
+    rb(g.ref[0], g.box, g.box + 3);
+    rb(g.ref[1], g.box + 6, g.box + 9);
+    bnode_box(g, lo, hi);
+  };
+  std::function<void(int, float*, float*)> rw = [&](int ref, float* lo, float* hi) {
+    if (ref_is_leaf(ref)) { leaf_box(tri, ref, lo, hi); return; }
+    WNode& q = c.qnodes[ref];
+    for (int i = 0; i < 4; i++) {
+      if (q.ref[i] == Q_EMPTY) continue;
+      float l[3], h[3];
+      rw(q.ref[i], l, h);
+      for (int a = 0; a < 3; a++) { q.lo[a][i] = l[a]; q.hi[a][i] = h[a]; }
+    }
+    wnode_box(q, lo, hi);
+  };
+  float lo[3], hi[3];
+  if (!ref_is_leaf(c.root)) rb(c.root, lo, hi);
+  if (c.qbuilt && !ref_is_leaf(c.qroot)) rw(c.qroot, lo, hi);
+}
+
+// Validation of one updated triangle's 18 floats: finite, positions below 2^30 in magnitude
+SCN_HD inline bool vertex_data_ok(const float* p1, const float* p2, const float* p3, const float* n1, const float* n2,
+                                  const float* n3) {
+  bool ok = true;
+  for (int a = 0; a < 3; a++) {
+    ok = ok && fabsf(p1[a]) < 0x1p30f && fabsf(p2[a]) < 0x1p30f && fabsf(p3[a]) < 0x1p30f;  // (false for NaN, inf)
+    ok = ok && trif::finitef_(n1[a]) && trif::finitef_(n2[a]) && trif::finitef_(n3[a]);
+  }
+  return ok;
+}
+
+// New vertices for `count` triangles of a compiled scene: t = first + i (tri_index NULL) or
+// tri_index[i] (first = 0).  p1..n3: float[3 * count].  Recomputes tri, trin.xyz, hrec and trx
+// (caps as compiled, extrema only growing), lets the culling bound grow, and refits both trees.
+// This is the definition; rt_update_geometry does the same on the device.  Returns RT_OK, or
+// RT_ERR_ARG with the reason in err and c untouched.
+inline int update_geometry(Compiled& c, const int32_t* tri_index, int first, int count, const float* p1, const float* p2,
+                           const float* p3, const float* n1, const float* n2, const float* n3, std::string& err) {
+  auto fail = [&](const char* msg) {
+    err = msg;
+    return (int)RT_ERR_ARG;
+  };
+  if (count < 0) return fail("negative count");
+  if (count == 0) return RT_OK;
+  if (!p1 || !p2 || !p3 || !n1 || !n2 || !n3) return fail("missing vertex arrays");
+  if (tri_index) {
+    if (first != 0) return fail("first must be 0 with an index list");
+    std::vector<char> seen((size_t)std::max(c.n_tri, 0), 0);
+    for (int i = 0; i < count; i++) {
+      const int t = tri_index[i];
+      if (t < 0 || t >= c.n_tri) return fail("triangle index out of range");
+      if (seen[t]) return fail("duplicate triangle index");
+      seen[t] = 1;
+    }
+  } else if (first < 0 || (int64_t)first + count > c.n_tri) {
+    return fail("range outside the triangle list");
+  }
+  for (int i = 0; i < count; i++)
+    if (!vertex_data_ok(p1 + 3 * i, p2 + 3 * i, p3 + 3 * i, n1 + 3 * i, n2 + 3 * i, n3 + 3 * i))
+      return fail("a position or normal is not finite, or a position is 2^30 or more");
+  CullStats cs{c.cull_R, c.cull_K, c.cull_off};
+  for (int i = 0; i < count; i++) {
+    const size_t t = (size_t)(tri_index ? tri_index[i] : first + i);
+    float* tri = &c.tri[12 * t];
+    float* trx = &c.trx[12 * t];
+    float scratch[12];
+    const bool was_flagged = !trif::within_caps(trif::tri_rows(tri, scratch), c.s_cap, c.sc_cap);
+    tri_record(p1 + 3 * i, p2 + 3 * i, p3 + 3 * i, n1 + 3 * i, n2 + 3 * i, n3 + 3 * i, tri, &c.trin[12 * t]);
+    hit_record(tri, &c.trin[12 * t], &c.hrec[32 * t]);
+    const trif::TriQ q = trif::tri_rows(tri, trx);
+    const bool flagged = !trif::within_caps(q, c.s_cap, c.sc_cap);
+    if (flagged) {
+      trx[4] = trx[5] = trx[6] = trx[8] = trx[9] = trx[10] = 0.0f;
+    } else {
+      c.s_max = std::max(c.s_max, q.S);
+      c.sc_max = std::max(c.sc_max, q.sc);
+      c.c_min = std::min(c.c_min, q.c);
+    }
+    c.tri_flagged += (int)flagged - (int)was_flagged;
+    cull_merge(cs, cull_tri(p1 + 3 * i, p2 + 3 * i, p3 + 3 * i));
+  }
+  c.cull_R = cs.R; c.cull_K = cs.K; c.cull_off = cs.off;
+  trif::Consts k;
+  k.s_max = c.s_max; k.sc_max = c.sc_max; k.c_min = c.c_min;
+  trif::form_margin(k);
+  c.tri_k1 = k.k1; c.tri_k0 = k.k0;
+  refit(c);
+  return RT_OK;
+}
+
+// The device's refit schedule.  Leaves: {ref, binary parent * 2 + side, 4-wide parent * 4 + slot, 0}
+// (-1: the root is the leaf / no 4-wide tree).  Internal nodes of each tree ordered by height (a
+// leaf is 0, a node 1 + the highest of its children): nodes of height h are list[off[h - 1] ..
+// off[h]), so every child of a node precedes it in an earlier group.
+struct RefitPlan {
+  std::vector<int32_t> leaves;          // 4 per leaf
+  std::vector<int32_t> blist, boff;     // boff[0] = 0, boff.size() = heights + 1
+  std::vector<int32_t> qlist, qoff;
+};
+inline RefitPlan refit_plan(const BNode* nodes, size_t n_nodes, int root, const WNode* qnodes, size_t n_qnodes, int qroot,
+                            bool qbuilt, bool has_scene, int n_tri) {
+  RefitPlan P;
+  P.boff.push_back(0);
+  P.qoff.push_back(0);
+  if (!has_scene) return P;
+  std::vector<int> leaf_at((size_t)std::max(n_tri, 0), -1);  // leaf index by its first triangle
+  auto group = [](const std::vector<int>& height, std::vector<int32_t>& list, std::vector<int32_t>& off) {
+    int hmax = 0;
+    for (int h : height) hmax = std::max(hmax, h);
+    off.assign((size_t)hmax + 1, 0);
+    for (int h : height) if (h > 0) off[h]++;
+    for (int h = 1; h <= hmax; h++) off[h] += off[h - 1];
+    list.assign((size_t)off[hmax], 0);
+    std::vector<int32_t> at(off.begin(), off.end());
+    for (size_t i = 0; i < height.size(); i++)
+      if (height[i] > 0) list[at[height[i] - 1]++] = (int32_t)i;
+  };
+  auto add_leaf = [&](int ref, int bslot) {
+    const int f = leaf_first(ref);
+    if (f >= 0 && f < n_tri && leaf_at[f] < 0) leaf_at[f] = (int)(P.leaves.size() / 4);
+    P.leaves.insert(P.leaves.end(), {ref, bslot, -1, 0});
+  };
+  if (ref_is_leaf(root)) {
+    add_leaf(root, -1);
+  } else {
+    std::vector<int> height(n_nodes, 0);
+    std::function<int(int)> hb = [&](int i) -> int {
+      int h = 0;
+      for (int k = 0; k < 2; k++) {
+        const int r = nodes[i].ref[k];
+        if (ref_is_leaf(r)) add_leaf(r, 2 * i + k);
+        else h = std::max(h, hb(r));
+      }
+      return height[i] = h + 1;
+    };
+    hb(root);
+    group(height, P.blist, P.boff);
+  }
+  if (qbuilt && !ref_is_leaf(qroot)) {
+    std::vector<int> height(n_qnodes, 0);
+    std::function<int(int)> hq = [&](int i) -> int {
+      int h = 0;
+      for (int k = 0; k < 4; k++) {
+        const int r = qnodes[i].ref[k];
+        if (r == Q_EMPTY) continue;
+        if (ref_is_leaf(r)) {
+          const int f = leaf_first(r);
+          if (f >= 0 && f < n_tri && leaf_at[f] >= 0) P.leaves[4 * (size_t)leaf_at[f] + 2] = 4 * i + k;
+        } else {
+          h = std::max(h, hq(r));
+        }
+      }
+      return height[i] = h + 1;
+    };
+    hq(qroot);
+    group(height, P.qlist, P.qoff);
+  }
+  return P;
+}
+inline RefitPlan refit_plan(const Compiled& c) {
+  return refit_plan(c.nodes.data(), c.nodes.size(), c.root, c.qnodes.data(), c.qnodes.size(), c.qroot, c.qbuilt,
+                    c.has_scene != 0, c.n_tri);
 }
 
 // The reference's own AoS encodings (Triangle_encoded: 14 texels, BVHNode_encoded: 4 texels) as an

@@ -35,10 +35,73 @@
 
 namespace trif {
 
+#ifdef __HIPCC__
+#define TRIF_HD __host__ __device__
+#else
+#define TRIF_HD
+#endif
+
+// The margin's constants and the state they are formed from: the two caps (fixed by build()) and
+// the extrema over the triangles that keep their rows.  scn::update_geometry moves triangles under
+// the same caps; the extrema then only grow (c_min only falls) until the next build().
 struct Consts {
   double k1 = 0.0, k0 = 0.0;
   int flagged = 0;  // triangles left to the reference's test alone
+  double s_cap = 0.0, sc_cap = 0.0;
+  double s_max = 0.0, sc_max = 0.0, c_min = 1.0;
 };
+
+// k1, k0 from the extrema (the two formulas of the header comment)
+inline void form_margin(Consts& k) {
+  const double u = 0x1p-24;
+  k.k1 = 2.0 * (72.9 * u / k.c_min + 5.2 * k.sc_max + 50.0 * u);
+  k.k0 = 2.0 * (24.3 * u * k.s_max + 2.0 * u);
+}
+
+// One triangle's part of build(): its record with the rows R2, R3 (zero rows when a per-triangle
+// condition fails) and the quantities the caps and the margin are taken over; S = sc = inf for a
+// triangle without rows.  The same code on the host and in the device's geometry update.
+struct TriQ {
+  double S, sc, c;
+};
+TRIF_HD inline double dmax_(double a, double b) { return a < b ? b : a; }
+TRIF_HD inline bool finite_(double x) { return x - x == 0.0; }
+TRIF_HD inline bool finitef_(float x) { return x - x == 0.0f; }
+TRIF_HD inline TriQ tri_rows(const float* A, float* O) {
+  TriQ q = {(double)INFINITY, (double)INFINITY, 0.0};
+  for (int j = 0; j < 4; j++) O[j] = A[j];
+  O[7] = A[7];
+  O[11] = A[11];
+  O[4] = O[5] = O[6] = O[8] = O[9] = O[10] = 0.0f;
+  const double p1[3] = {A[0], A[1], A[2]}, p2[3] = {A[4], A[5], A[6]}, p3[3] = {A[8], A[9], A[10]};
+  const double N[3] = {A[3], A[7], A[11]};
+  if (!(finite_(N[0]) && finite_(N[1]) && finite_(N[2]))) return q;  // never reaches the edges
+  double E2[3], E3[3], E23[3];
+  for (int a = 0; a < 3; a++) { E2[a] = p2[a] - p1[a]; E3[a] = p3[a] - p1[a]; E23[a] = p3[a] - p2[a]; }
+  const double n[3] = {E2[1] * E3[2] - E2[2] * E3[1], E2[2] * E3[0] - E2[0] * E3[2], E2[0] * E3[1] - E2[1] * E3[0]};
+  const double nn2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2], nn = sqrt(nn2);
+  if (!(nn > 0.0) || !finite_(nn2)) return q;
+  const double c = (N[0] * n[0] + N[1] * n[1] + N[2] * n[2]) / nn;
+  const double x[3] = {N[1] * n[2] - N[2] * n[1], N[2] * n[0] - N[0] * n[2], N[0] * n[1] - N[1] * n[0]};
+  const double s = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) / nn;
+  if (!(c > 0.5)) return q;
+  double amax = 0.0;
+  for (int a = 0; a < 3; a++) amax = dmax_(dmax_(dmax_(amax, fabs(E2[a])), fabs(E3[a])), fabs(E23[a]));
+  const double R2[3] = {(E3[1] * n[2] - E3[2] * n[1]) / nn2, (E3[2] * n[0] - E3[0] * n[2]) / nn2,
+                        (E3[0] * n[1] - E3[1] * n[0]) / nn2};
+  const double R3[3] = {(n[1] * E2[2] - n[2] * E2[1]) / nn2, (n[2] * E2[0] - n[0] * E2[2]) / nn2,
+                        (n[0] * E2[1] - n[1] * E2[0]) / nn2};
+  bool fin = true;
+  for (int a = 0; a < 3; a++) fin = fin && finitef_((float)R2[a]) && finitef_((float)R3[a]);
+  if (!fin) return q;
+  for (int a = 0; a < 3; a++) { O[4 + a] = (float)R2[a]; O[8 + a] = (float)R3[a]; }
+  q.S = amax * amax / (nn * c);
+  q.sc = s / c;
+  q.c = c;
+  return q;
+}
+// Whether a triangle with these quantities keeps its rows under the caps
+TRIF_HD inline bool within_caps(const TriQ& q, double s_cap, double sc_cap) { return q.S <= s_cap && q.sc <= sc_cap; }
 
 // tri: 3 float[4] per triangle {p1, N.x} {p2, N.y} {p3, N.z} (N = the reference's fp32 normal).
 // out: 3 float[4] per triangle {p1, N.x} {R2, N.y} {R3, N.z}.
@@ -46,37 +109,10 @@ inline Consts build(const float* tri, long nt, float* out) {
   const double u = 0x1p-24;
   std::vector<double> S(nt, INFINITY), sc(nt, INFINITY), cs(nt, 0.0);
   for (long i = 0; i < nt; i++) {
-    const float* A = tri + 12 * i;
-    float* O = out + 12 * i;
-    std::memcpy(O, A, 16);
-    O[7] = A[7];
-    O[11] = A[11];
-    O[4] = O[5] = O[6] = O[8] = O[9] = O[10] = 0.0f;
-    const double p1[3] = {A[0], A[1], A[2]}, p2[3] = {A[4], A[5], A[6]}, p3[3] = {A[8], A[9], A[10]};
-    const double N[3] = {A[3], A[7], A[11]};
-    if (!(std::isfinite(N[0]) && std::isfinite(N[1]) && std::isfinite(N[2]))) continue;  // never reaches the edges
-    double E2[3], E3[3], E23[3];
-    for (int a = 0; a < 3; a++) { E2[a] = p2[a] - p1[a]; E3[a] = p3[a] - p1[a]; E23[a] = p3[a] - p2[a]; }
-    const double n[3] = {E2[1] * E3[2] - E2[2] * E3[1], E2[2] * E3[0] - E2[0] * E3[2], E2[0] * E3[1] - E2[1] * E3[0]};
-    const double nn2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2], nn = std::sqrt(nn2);
-    if (!(nn > 0.0) || !std::isfinite(nn2)) continue;
-    const double c = (N[0] * n[0] + N[1] * n[1] + N[2] * n[2]) / nn;
-    const double x[3] = {N[1] * n[2] - N[2] * n[1], N[2] * n[0] - N[0] * n[2], N[0] * n[1] - N[1] * n[0]};
-    const double s = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) / nn;
-    if (!(c > 0.5)) continue;
-    double amax = 0.0;
-    for (int a = 0; a < 3; a++) amax = std::max({amax, std::fabs(E2[a]), std::fabs(E3[a]), std::fabs(E23[a])});
-    const double R2[3] = {(E3[1] * n[2] - E3[2] * n[1]) / nn2, (E3[2] * n[0] - E3[0] * n[2]) / nn2,
-                          (E3[0] * n[1] - E3[1] * n[0]) / nn2};
-    const double R3[3] = {(n[1] * E2[2] - n[2] * E2[1]) / nn2, (n[2] * E2[0] - n[0] * E2[2]) / nn2,
-                          (n[0] * E2[1] - n[1] * E2[0]) / nn2};
-    bool fin = true;
-    for (int a = 0; a < 3; a++) fin = fin && std::isfinite((float)R2[a]) && std::isfinite((float)R3[a]);
-    if (!fin) continue;
-    for (int a = 0; a < 3; a++) { O[4 + a] = (float)R2[a]; O[8 + a] = (float)R3[a]; }
-    S[i] = amax * amax / (nn * c);
-    sc[i] = s / c;
-    cs[i] = c;
+    const TriQ q = tri_rows(tri + 12 * i, out + 12 * i);
+    S[i] = q.S;
+    sc[i] = q.sc;
+    cs[i] = q.c;
   }
   // cap: the 99.9th percentile, but at most 16x the median (a scene with many slivers keeps the
   // margin of its well-shaped triangles; the slivers take the reference's test)
@@ -90,22 +126,21 @@ inline Consts build(const float* tri, long nt, float* out) {
     std::nth_element(f.begin(), f.begin() + (long)(f.size() / 2), f.end());
     return std::max(floor_, std::min(hi, 16.0 * f[f.size() / 2]));
   };
-  const double s_cap = cap(S, 8.0), sc_cap = cap(sc, 4.0 * u);
   Consts k;
-  double s_max = 0.0, sc_max = 0.0, c_min = 1.0;
+  k.s_cap = cap(S, 8.0);
+  k.sc_cap = cap(sc, 4.0 * u);
   for (long i = 0; i < nt; i++) {
     float* O = out + 12 * i;
-    if (!(S[i] <= s_cap && sc[i] <= sc_cap)) {
+    if (!within_caps(TriQ{S[i], sc[i], cs[i]}, k.s_cap, k.sc_cap)) {
       O[4] = O[5] = O[6] = O[8] = O[9] = O[10] = 0.0f;
       k.flagged++;
       continue;
     }
-    s_max = std::max(s_max, S[i]);
-    sc_max = std::max(sc_max, sc[i]);
-    c_min = std::min(c_min, cs[i]);
+    k.s_max = std::max(k.s_max, S[i]);
+    k.sc_max = std::max(k.sc_max, sc[i]);
+    k.c_min = std::min(k.c_min, cs[i]);
   }
-  k.k1 = 2.0 * (72.9 * u / c_min + 5.2 * sc_max + 50.0 * u);
-  k.k0 = 2.0 * (24.3 * u * s_max + 2.0 * u);
+  form_margin(k);
   return k;
 }
 

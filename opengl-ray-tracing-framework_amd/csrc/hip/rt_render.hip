@@ -36,6 +36,7 @@
 #endif
 #include "scene_compile.h"
 #include "dev_layout.h"
+#include "rt_geometry.h"
 
 using rtd::GNode;
 using rtd::KParams;
@@ -61,6 +62,24 @@ struct rt_ctx {
   int n_tri = 0, n_mats = 0, root = 0, has_scene = 0, stack_entries = 2;
   double cull_R = 0.0, cull_K = 0.0, cull_off = 0.0;  // culling bound of the scene (cull_bound_stats)
   bool scene_set = false;
+  // what rt_update_geometry needs of the compile: the edge filter's state (trif::Consts), whether
+  // d_qnodes holds a 4-wide tree, the binary node count and the six scene arrays' sizes in bytes
+  double s_cap = 0.0, sc_cap = 0.0, s_max = 0.0, sc_max = 0.0, c_min = 1.0;
+  bool qbuilt = false;
+  int n_nodes = 0;
+  size_t scene_bytes[6] = {};  // indexed by RT_SCENE_*
+  // rt_update_geometry's refit schedule (scn::refit_plan) and staging: built by the first update
+  // after a rt_set_scene, from the node arrays as they stand on the device
+  struct Geometry {
+    bool planned = false;
+    int4* d_leaves = nullptr;
+    int n_leaves = 0;
+    int *d_blist = nullptr, *d_boff = nullptr, *d_qlist = nullptr, *d_qoff = nullptr;
+    std::vector<int32_t> boff, qoff;
+    rtg::Red* d_red = nullptr;
+    float* d_stage = nullptr;  // the host form's vertex arrays (18 floats per triangle), then its indices
+    size_t stage_tris = 0;
+  } geo;
   std::vector<int32_t> tri_mat;  // host copy of the per-triangle material ids (for updates)
   std::vector<float> mat_table;  // host copy, 32 floats per material
   // some material's emission is not +0 (all bits): an emissive camera hit needs s2.w for Le0.y, so
@@ -702,6 +721,57 @@ int alloc_wavefront(rt_ctx* c, size_t paths) {
   return RT_OK;
 }
 
+// The refit schedule of rt_update_geometry (the next update builds the current tree's)
+void geo_drop(rt_ctx* c) {
+  rt_ctx::Geometry& g = c->geo;
+  dfree(g.d_leaves); dfree(g.d_blist); dfree(g.d_boff); dfree(g.d_qlist); dfree(g.d_qoff);
+  g.n_leaves = 0;
+  g.boff.clear();
+  g.qoff.clear();
+  g.planned = false;
+}
+
+// ---- rt_update_geometry (rt_geometry.h; the definition is scn::update_geometry)
+// The refit schedule and the reduction cell, on the first update after a rt_set_scene: the node
+// arrays come from the device, so a context that never updates geometry keeps no copy of them
+int geo_prepare(rt_ctx* c) {
+  rt_ctx::Geometry& g = c->geo;
+  if (!g.d_red) HIPCHK(c, hipMalloc(&g.d_red, sizeof(rtg::Red)));
+  if (g.planned) return RT_OK;
+  std::vector<scn::BNode> nodes((size_t)c->n_nodes);
+  std::vector<scn::WNode> qnodes((size_t)c->n_qnodes);
+  HIPCHK(c, hipMemcpy(nodes.data(), c->d_nodes, nodes.size() * sizeof(scn::BNode), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(qnodes.data(), c->d_qnodes, qnodes.size() * sizeof(scn::WNode), hipMemcpyDeviceToHost));
+  const scn::RefitPlan P = scn::refit_plan(nodes.data(), nodes.size(), c->root, qnodes.data(), qnodes.size(), c->qroot,
+                                           c->qbuilt, c->has_scene != 0, c->n_tri);
+  int rc;
+  if ((rc = upload(c, (void**)&g.d_leaves, P.leaves.data(), P.leaves.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload(c, (void**)&g.d_blist, P.blist.data(), P.blist.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload(c, (void**)&g.d_boff, P.boff.data(), P.boff.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload(c, (void**)&g.d_qlist, P.qlist.data(), P.qlist.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload(c, (void**)&g.d_qoff, P.qoff.data(), P.qoff.size() * sizeof(int32_t)))) return rc;
+  g.n_leaves = (int)(P.leaves.size() / 4);
+  g.boff = P.boff;
+  g.qoff = P.qoff;
+  g.planned = true;
+  return RT_OK;
+}
+
+// The internal nodes of one tree, lowest height first: one launch per height, and one
+// single-workgroup launch for the top heights from the first one on after which every height's
+// nodes fit a workgroup
+template <typename Node, typename Kernel>
+void geo_refit_tree(rt_ctx* c, Kernel kernel, Node* nodes, const int* d_list, const int* d_off,
+                           const std::vector<int32_t>& off) {
+  const int H = (int)off.size() - 1;  // heights 1 .. H
+  int top = H + 1;
+  while (top > 1 && off[top - 1] - off[top - 2] <= 256) top--;
+  for (int h = 1; h < top; h++)
+    hipLaunchKernelGGL(kernel, dim3((off[h] - off[h - 1] + 255) / 256), dim3(256), 0, c->stream, nodes, d_list, d_off, h,
+                       h + 1);
+  if (top <= H) hipLaunchKernelGGL(kernel, dim3(1), dim3(256), 0, c->stream, nodes, d_list, d_off, top, H + 1);
+}
+
 }  // namespace
 
 extern "C" {
@@ -749,6 +819,8 @@ int rt_destroy(rt_ctx* c) {
     if (t.last_use) (void)hipEventDestroy(t.last_use);
     if (t.built) (void)hipEventDestroy(t.built);
   }
+  geo_drop(c);
+  dfree(c->geo.d_red); dfree(c->geo.d_stage);
   dfree(c->d_hdr); dfree(c->d_cache); dfree(c->d_accum); dfree(c->d_counter); dfree(c->d_stats);
   for (auto& e : c->trace_events) { (void)hipEventDestroy(e.s); (void)hipEventDestroy(e.e); }
   for (auto e : c->event_pool) (void)hipEventDestroy(e);
@@ -804,6 +876,7 @@ int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   // without one (renders and queries then refuse) rather than with a mix of old and new buffers
   c->scene_set = false;
   c->tp.drop();  // the display history shows another scene
+  geo_drop(c);   // and the refit schedule is another tree's
   int rc;
   if ((rc = upload(c, (void**)&c->d_qnodes, k.qnodes.data(), k.qnodes.size() * sizeof(scn::WNode)))) return rc;
   if ((rc = upload(c, (void**)&c->d_nodes, k.nodes.data(), k.nodes.size() * sizeof(scn::BNode)))) return rc;
@@ -823,6 +896,15 @@ int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   c->wide = k.wide;
   c->qroot = k.qroot;
   c->qstack_entries = std::max(2, 3 * k.qdepth + 2);
+  c->s_cap = k.s_cap; c->sc_cap = k.sc_cap; c->s_max = k.s_max; c->sc_max = k.sc_max; c->c_min = k.c_min;
+  c->qbuilt = k.qbuilt;
+  c->n_nodes = (int)k.nodes.size();
+  {
+    const size_t b[6] = {k.tri.size() * sizeof(float), k.trx.size() * sizeof(float), k.trin.size() * sizeof(float),
+                         k.hrec.size() * sizeof(float), k.nodes.size() * sizeof(scn::BNode),
+                         k.qnodes.size() * sizeof(scn::WNode)};
+    std::copy(b, b + 6, c->scene_bytes);
+  }
   c->tri_mat = std::move(k.tri_mat);
   c->mat_table = std::move(k.mats);
   c->mats_emissive = table_emissive(c->mat_table);
@@ -864,6 +946,134 @@ int rt_update_materials(rt_ctx* c, int32_t first, int32_t count, const rt_materi
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ---- rt_update_geometry (rt_geometry.h; the definition is scn::update_geometry)
+int rt_update_geometry_device(rt_ctx* c, const void* tri_index_dev, int32_t first, int32_t count, const void* p1,
+                              const void* p2, const void* p3, const void* n1, const void* n2, const void* n3) {
+  if (!c) return RT_ERR_ARG;
+  if (count < 0) return fail(c, RT_ERR_ARG, "negative count");
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "no scene");
+  if (count == 0) return RT_OK;
+  if (!p1 || !p2 || !p3 || !n1 || !n2 || !n3) return fail(c, RT_ERR_ARG, "missing vertex arrays");
+  if (tri_index_dev && first != 0) return fail(c, RT_ERR_ARG, "first must be 0 with an index list");
+  if (!tri_index_dev && (first < 0 || (int64_t)first + count > c->n_tri))
+    return fail(c, RT_ERR_ARG, "range outside the triangle list");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = drain(c)) return rc;
+  if (int rc = geo_prepare(c)) return rc;
+  rt_ctx::Geometry& g = c->geo;
+  auto bits = [](double x) {
+    unsigned long long b;
+    memcpy(&b, &x, 8);
+    return b;
+  };
+  auto value = [](unsigned long long b) {
+    double x;
+    memcpy(&x, &b, 8);
+    return x;
+  };
+  rtg::Red red{bits(c->cull_R), bits(c->cull_K), bits(c->cull_off), bits(c->s_max), bits(c->sc_max), bits(c->c_min), 0, 0};
+  HIPCHK(c, hipMemcpyAsync(g.d_red, &red, sizeof(red), hipMemcpyHostToDevice, c->stream));
+  const dim3 grid((count + 255) / 256), block(256);
+  const int* idx = static_cast<const int*>(tri_index_dev);
+  const float *q1 = static_cast<const float*>(p1), *q2 = static_cast<const float*>(p2), *q3 = static_cast<const float*>(p3);
+  const float *m1 = static_cast<const float*>(n1), *m2 = static_cast<const float*>(n2), *m3 = static_cast<const float*>(n3);
+  hipLaunchKernelGGL(rtg::geo_check, grid, block, 0, c->stream, idx, first, count, c->n_tri, q1, q2, q3, m1, m2, m3, c->s_cap,
+                     c->sc_cap, g.d_red);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&red, g.d_red, sizeof(red), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (red.bad)  // (nothing of the scene has been written)
+    return fail(c, RT_ERR_ARG, "a triangle index is out of range, a value is not finite or a position is 2^30 or more");
+  hipLaunchKernelGGL(rtg::geo_record, grid, block, 0, c->stream, idx, first, count, q1, q2, q3, m1, m2, m3, c->s_cap, c->sc_cap,
+                     c->d_tri, c->d_trx, c->d_trin, c->d_hrec, g.d_red);
+  HIPCHK(c, hipGetLastError());
+  c->dn.guides = false;  // the denoise / temporal guides show the old surfaces (the history stays: the caller resets)
+  if (g.n_leaves > 0) {
+    hipLaunchKernelGGL(rtg::geo_leaf, dim3((g.n_leaves + 255) / 256), block, 0, c->stream, g.d_leaves, g.n_leaves, c->d_tri,
+                       reinterpret_cast<scn::BNode*>(c->d_nodes), reinterpret_cast<scn::WNode*>(c->d_qnodes));
+    geo_refit_tree(c, rtg::geo_refit_b, reinterpret_cast<scn::BNode*>(c->d_nodes), g.d_blist, g.d_boff, g.boff);
+    geo_refit_tree(c, rtg::geo_refit_q, reinterpret_cast<scn::WNode*>(c->d_qnodes), g.d_qlist, g.d_qoff, g.qoff);
+    HIPCHK(c, hipGetLastError());
+  }
+  int delta = 0;
+  HIPCHK(c, hipMemcpyAsync(&delta, &g.d_red->flag_delta, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // the constants the next call turns into kernel arguments (fill_scene_kparams): none shrinks
+  c->cull_R = value(red.R); c->cull_K = value(red.K); c->cull_off = value(red.off);
+  c->s_max = value(red.s_max); c->sc_max = value(red.sc_max); c->c_min = value(red.c_min);
+  trif::Consts k;
+  k.s_max = c->s_max; k.sc_max = c->sc_max; k.c_min = c->c_min;
+  trif::form_margin(k);
+  c->tri_k1 = k.k1; c->tri_k0 = k.k0;
+  c->tri_flagged += delta;
+  return RT_OK;
+}
+
+int rt_update_geometry(rt_ctx* c, const int32_t* tri_index, int32_t first, int32_t count, const float* p1, const float* p2,
+                       const float* p3, const float* n1, const float* n2, const float* n3) {
+  if (!c) return RT_ERR_ARG;
+  if (count < 0) return fail(c, RT_ERR_ARG, "negative count");
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "no scene");
+  if (count == 0) return RT_OK;
+  if (!p1 || !p2 || !p3 || !n1 || !n2 || !n3) return fail(c, RT_ERR_ARG, "missing vertex arrays");
+  if (tri_index) {  // (the device form cannot see a duplicate: two lanes would write one triangle)
+    if (first != 0) return fail(c, RT_ERR_ARG, "first must be 0 with an index list");
+    std::vector<char> seen((size_t)c->n_tri, 0);
+    for (int i = 0; i < count; i++) {
+      const int t = tri_index[i];
+      if (t < 0 || t >= c->n_tri) return fail(c, RT_ERR_ARG, "triangle index out of range");
+      if (seen[t]) return fail(c, RT_ERR_ARG, "duplicate triangle index");
+      seen[t] = 1;
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = drain(c)) return rc;  // (the staging of the previous update is no longer read)
+  rt_ctx::Geometry& g = c->geo;
+  if (g.stage_tris < (size_t)count) {
+    dfree(g.d_stage);
+    g.stage_tris = 0;
+    HIPCHK(c, hipMalloc(&g.d_stage, (size_t)count * 19 * sizeof(float)));
+    g.stage_tris = (size_t)count;
+  }
+  const size_t n3f = 3 * (size_t)count;
+  const float* src[6] = {p1, p2, p3, n1, n2, n3};
+  for (int k = 0; k < 6; k++)
+    HIPCHK(c, hipMemcpyAsync(g.d_stage + k * n3f, src[k], n3f * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  int* d_idx = reinterpret_cast<int*>(g.d_stage + 6 * n3f);
+  if (tri_index) HIPCHK(c, hipMemcpyAsync(d_idx, tri_index, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return rt_update_geometry_device(c, tri_index ? d_idx : nullptr, first, count, g.d_stage, g.d_stage + n3f,
+                                   g.d_stage + 2 * n3f, g.d_stage + 3 * n3f, g.d_stage + 4 * n3f, g.d_stage + 5 * n3f);
+}
+
+int rt_scene_download(rt_ctx* c, int32_t which, void* out, size_t bytes) {
+  if (!c) return RT_ERR_ARG;
+  if (which < 0 || which > RT_SCENE_QNODES || !out) return fail(c, RT_ERR_ARG, "unknown array or null output");
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "no scene");
+  if (bytes != c->scene_bytes[which]) return fail(c, RT_ERR_ARG, "the array has another size");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = drain(c)) return rc;
+  const void* src[6] = {c->d_tri, c->d_trx, c->d_trin, c->d_hrec, c->d_nodes, c->d_qnodes};
+  HIPCHK(c, hipMemcpy(out, src[which], bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_scene_array_bytes(rt_ctx* c, int32_t which, size_t* bytes) {
+  if (!c) return RT_ERR_ARG;
+  if (which < 0 || which > RT_SCENE_QNODES || !bytes) return fail(c, RT_ERR_ARG, "unknown array or null output");
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "no scene");
+  *bytes = c->scene_bytes[which];
+  return RT_OK;
+}
+
+int rt_scene_bounds(rt_ctx* c, double out[5], int32_t* tri_flagged) {
+  if (!c) return RT_ERR_ARG;
+  if (!out) return fail(c, RT_ERR_ARG, "null output");
+  if (!c->scene_set) return fail(c, RT_ERR_STATE, "no scene");
+  out[0] = c->cull_R; out[1] = c->cull_K; out[2] = c->cull_off; out[3] = c->tri_k1; out[4] = c->tri_k0;
+  if (tri_flagged) *tri_flagged = c->tri_flagged;
   return RT_OK;
 }
 

@@ -1378,6 +1378,7 @@ int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_
 struct rts_compiled {
   scn::Compiled c;
   std::string err;
+  scn::RefitPlan plan;  // what rts_refit_plan last returned a view of
 };
 
 static scn::Options compile_options(const int32_t* o) {
@@ -1416,3 +1417,26 @@ int rts_compiled_get(const rts_compiled* k, rts_compiled_view* v) {
 }
 
 void rts_compiled_free(rts_compiled* k) { delete k; }
+
+int rts_compiled_update_geometry(rts_compiled* k, const int32_t* tri_index, int32_t first, int32_t count, const float* p1,
+                                 const float* p2, const float* p3, const float* n1, const float* n2, const float* n3) {
+  if (!k) return RTS_ERR_ARG;
+  return scn::update_geometry(k->c, tri_index, first, count, p1, p2, p3, n1, n2, n3, k->err);
+}
+
+int rts_compiled_filter_state(const rts_compiled* k, double out[5]) {
+  if (!k || !out) return RTS_ERR_ARG;
+  const scn::Compiled& c = k->c;
+  out[0] = c.s_cap; out[1] = c.sc_cap; out[2] = c.s_max; out[3] = c.sc_max; out[4] = c.c_min;
+  return RTS_OK;
+}
+
+int rts_refit_plan(rts_compiled* k, rts_refit_plan_view* v) {
+  if (!k || !v) return RTS_ERR_ARG;
+  k->plan = scn::refit_plan(k->c);
+  const scn::RefitPlan& p = k->plan;
+  *v = rts_refit_plan_view{p.leaves.data(), p.blist.data(), p.boff.data(), p.qlist.data(), p.qoff.data(),
+                           (int32_t)(p.leaves.size() / 4), (int32_t)p.blist.size(), (int32_t)p.boff.size(),
+                           (int32_t)p.qlist.size(), (int32_t)p.qoff.size()};
+  return RTS_OK;
+}

@@ -119,6 +119,8 @@ class SceneData:
     soa: dict
     nodes: dict
     ranges: List[tuple]   # pre-BVH triangle range per object
+    objects: tuple = ()   # the Obj list the scene was built from
+    pre_to_post: np.ndarray = None  # post-BVH index of each pre-BVH triangle (rts_scene_post_bvh_index)
 
 
 def build_scene(objects, leaf_size: int = 8) -> SceneData:
@@ -130,7 +132,8 @@ def build_scene(objects, leaf_size: int = 8) -> SceneData:
         ranges.append(s.add_mesh(load_mesh(o.mesh), mat, o.rotate, o.translate, o.scale, o.smooth))
     s.build_bvh(leaf_size)
     tri, nodes = s.encode()
-    return SceneData("custom", s.counts(), tri, nodes, s.export_soa(), s.nodes(), ranges)
+    return SceneData("custom", s.counts(), tri, nodes, s.export_soa(), s.nodes(), ranges, tuple(objects),
+                     s.post_bvh_index())
 
 
 @lru_cache(maxsize=None)

@@ -136,6 +136,7 @@ class Input:
     camera_rotation: Optional[Sequence[float]] = None   # InputFloat3 "Camera Rotation"
     camera_zoom: Optional[float] = None                 # SliderFloat "Camera Zoom"
     materials: Sequence[tuple] = ()             # (first_triangle, count, sl.Material): setDirty()
+    geometry: Sequence[tuple] = ()              # (tri_index or None, p, n): Renderer.update_geometry, LoopNum = 0
     resize: Optional[tuple] = None              # (width, height)
     pick: Optional[tuple] = None                # cursor (xpos, ypos), window coordinates like `mouse`
 
@@ -233,6 +234,9 @@ class Session:
             self.camera.refresh()
         for first, count, mat in inp.materials:  # setDirty(): RefreshTriangleMaterial + LoopNum = 0
             self.r.update_materials(first, count, mat.texels())
+            reset = True
+        for tri_index, p, n in inp.geometry:  # moved triangles: the accumulation restarts, as after a material edit
+            self.r.update_geometry(tri_index, p, n)
             reset = True
         if self.camera.take_reset() or reset:
             self.r.reset()

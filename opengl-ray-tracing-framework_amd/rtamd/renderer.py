@@ -50,11 +50,16 @@ ABI_SYMBOLS = (
     "rt_get_triangle_material",
     "rt_denoise_default_params", "rt_denoise_async", "rt_denoise",
     "rt_temporal_default_params", "rt_temporal_async", "rt_temporal", "rt_temporal_history",
+    "rt_update_geometry", "rt_update_geometry_device", "rt_scene_download", "rt_scene_array_bytes",
+    "rt_scene_bounds",
 )
 RT_DISPLAY_TONEMAP, RT_DISPLAY_GAMMA = 1, 2
 RT_HAS_DENOISE = 1
 RT_DENOISE_REUSE_GUIDES = 1
 RT_HAS_TEMPORAL = 1
+RT_HAS_GEOMETRY_UPDATE = 1
+# rt_scene_download's arrays and the dtype / row shape each comes back as
+SCENE_ARRAYS = ("tri", "trx", "trin", "hrec", "nodes", "qnodes")
 RT_TEMPORAL_ADVANCE, RT_TEMPORAL_REUSE_GUIDES, RT_TEMPORAL_RESET = 1, 2, 4
 
 
@@ -328,6 +333,12 @@ def _bind(L: C.CDLL) -> C.CDLL:
         L.rt_temporal_async.argtypes = [vp, fpp, tpp, vp, vp, C.POINTER(vp)]
         L.rt_temporal.argtypes = [vp, fpp, tpp, _f32p]
         L.rt_temporal_history.argtypes = [vp, _f32p]
+    if hasattr(L, "rt_update_geometry"):  # RT_HAS_GEOMETRY_UPDATE (likewise)
+        L.rt_update_geometry.argtypes = [vp, _i32p, C.c_int32, C.c_int32] + [_f32p] * 6
+        L.rt_update_geometry_device.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 6
+        L.rt_scene_download.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+        L.rt_scene_array_bytes.argtypes = [vp, C.c_int32, C.POINTER(C.c_size_t)]
+        L.rt_scene_bounds.argtypes = [vp, C.POINTER(C.c_double), _i32p]
     return L
 
 
@@ -392,6 +403,62 @@ class Renderer:
         for k, v in enumerate(np.asarray(material_texels, np.float32).reshape(24)):
             m.v[k] = float(v)
         self._check(self._L.rt_update_materials(self._h, first, count, C.byref(m)), "rt_update_materials")
+
+    def update_geometry(self, tri_index, p, n, first: int = 0) -> None:
+        """rt_update_geometry: new vertices for triangles tri_index (or first .. first + count when
+        tri_index is None); p, n: (count, 3, 3) positions and normals [triangle, vertex, xyz].
+        numpy arrays go through the host form; torch tensors on the context's device through
+        rt_update_geometry_device (distinct indices are then the caller's contract)."""
+        if type(p).__module__.startswith("torch"):
+            import torch
+            p = p.to(torch.float32).reshape(-1, 3, 3)
+            n = n.to(torch.float32).reshape(-1, 3, 3)
+            if not (p.is_cuda and n.is_cuda) or p.shape != n.shape:
+                raise ValueError("p and n must be device tensors of one shape (count, 3, 3)")
+            count = p.shape[0]
+            arrs = [a[:, k].contiguous() for a in (p, n) for k in range(3)]
+            idx = None
+            if tri_index is not None:
+                idx = torch.as_tensor(tri_index, device=p.device).to(torch.int32).contiguous()
+                if idx.numel() != count:
+                    raise ValueError("one index per triangle")
+            torch.cuda.current_stream(p.device).synchronize()  # the arrays are complete before the ctx stream reads them
+            self._check(self._L.rt_update_geometry_device(
+                self._h, C.c_void_p(idx.data_ptr()) if idx is not None and count else None, int(first), count,
+                *[C.c_void_p(a.data_ptr()) if count else None for a in arrs]), "rt_update_geometry_device")
+            return
+        from .scene_lib import split_vertices
+        arrs = split_vertices(p, n)
+        count = arrs[0].shape[0]
+        idx = None if tri_index is None else np.ascontiguousarray(tri_index, np.int32)
+        if idx is not None and idx.size != count:
+            raise ValueError("one index per triangle")
+        self._check(self._L.rt_update_geometry(self._h, _ip(idx), int(first), count, *[_fp(a) for a in arrs]),
+                    "rt_update_geometry")
+
+    def scene_download(self, which: str) -> np.ndarray:
+        """rt_scene_download: the device array `which` (SCENE_ARRAYS) as it stands: tri, trx, trin, hrec
+        as (n, 4) float32, nodes / qnodes as scene_lib.BNODE_DTYPE / WNODE_DTYPE records."""
+        from .scene_lib import BNODE_DTYPE, WNODE_DTYPE
+        k = SCENE_ARRAYS.index(which)
+        nbytes = C.c_size_t()
+        self._check(self._L.rt_scene_array_bytes(self._h, k, C.byref(nbytes)), "rt_scene_array_bytes")
+        out = np.zeros(nbytes.value, np.uint8)
+        self._check(self._L.rt_scene_download(self._h, k, out.ctypes.data, out.nbytes), "rt_scene_download")
+        if which == "nodes":
+            return out.view(BNODE_DTYPE)
+        if which == "qnodes":
+            return out.view(WNODE_DTYPE)
+        return out.view(np.float32).reshape(-1, 4)
+
+    def scene_bounds(self) -> dict:
+        """rt_scene_bounds: cull_R, cull_K, cull_off, tri_k1, tri_k0 and tri_flagged."""
+        out = (C.c_double * 5)()
+        fl = C.c_int32()
+        self._check(self._L.rt_scene_bounds(self._h, out, C.byref(fl)), "rt_scene_bounds")
+        d = dict(zip(("cull_R", "cull_K", "cull_off", "tri_k1", "tri_k0"), list(out)))
+        d["tri_flagged"] = fl.value
+        return d
 
     def set_env(self, hdr: np.ndarray, cache: np.ndarray, hdr_resolution: Optional[int] = None) -> None:
         a = np.ascontiguousarray(hdr, np.float32)

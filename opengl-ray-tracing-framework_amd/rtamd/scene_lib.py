@@ -92,6 +92,11 @@ class RtsCompiledView(C.Structure):
                 + [("err", C.c_char_p)])
 
 
+class RtsRefitPlanView(C.Structure):
+    _fields_ = ([(k, _i32p) for k in ("leaves", "blist", "boff", "qlist", "qoff")]
+                + [(k, C.c_int32) for k in ("n_leaves", "n_blist", "n_boff", "n_qlist", "n_qoff")])
+
+
 # the scene compiler's records (csrc/common/scene_compile.h scn::BNode, scn::WNode)
 BNODE_DTYPE = np.dtype([("box", np.float32, 12), ("ref", np.int32, 4)])
 WNODE_DTYPE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("ref", np.int32, 4),
@@ -145,6 +150,9 @@ def lib() -> C.CDLL:
         L.rts_compiled_get.argtypes = [vp, C.POINTER(RtsCompiledView)]
         L.rts_compiled_free.argtypes = [vp]
         L.rts_compiled_free.restype = None
+        L.rts_compiled_update_geometry.argtypes = [vp, _i32p, C.c_int32, C.c_int32] + [_f32p] * 6
+        L.rts_compiled_filter_state.argtypes = [vp, C.POINTER(C.c_double)]
+        L.rts_refit_plan.argtypes = [vp, C.POINTER(RtsRefitPlanView)]
         _lib = L
     return _lib
 
@@ -408,7 +416,7 @@ class CompiledScene:
     scalars: dict
 
 
-def _compiled(rc: int, h) -> CompiledScene:
+def _compiled(rc: int, h, keep: bool = False) -> CompiledScene:
     L = lib()
     try:
         v = RtsCompiledView()
@@ -429,7 +437,66 @@ def _compiled(rc: int, h) -> CompiledScene:
         sc["wide"] = bool(v.wide)
         return CompiledScene(rc, (v.err or b"").decode(), a, sc)
     finally:
-        L.rts_compiled_free(h)
+        if not keep:
+            L.rts_compiled_free(h)
+
+
+def split_vertices(p, n, count=None):
+    """(count, 3, 3) positions and normals [triangle, vertex, xyz] -> the six float[3 * count] arrays
+    p1, p2, p3, n1, n2, n3 of the geometry update calls."""
+    p = np.asarray(p, np.float32).reshape(-1, 3, 3)
+    n = np.asarray(n, np.float32).reshape(-1, 3, 3)
+    if p.shape != n.shape or (count is not None and p.shape[0] != count):
+        raise ValueError("positions and normals must be (count, 3, 3)")
+    return [np.ascontiguousarray(a[:, k]) for a in (p, n) for k in range(3)]
+
+
+class CompiledHandle:
+    """A compiled scene that stays alive, for the geometry update's CPU model
+    (rts_compiled_update_geometry = scn::update_geometry, the definition the device follows)."""
+
+    def __init__(self, tri_enc: np.ndarray, node_enc: np.ndarray, *, rebuild=True, greedy=False, bfs=True, wide=True):
+        t = np.ascontiguousarray(tri_enc, np.float32)
+        n = np.ascontiguousarray(node_enc, np.float32)
+        self._h = C.c_void_p()
+        self.rc = lib().rts_compile_scene_encoded(_fp(t), t.shape[0], _fp(n), n.shape[0],
+                                                  _ip(_options(rebuild, greedy, bfs, wide)), C.byref(self._h))
+        if not self._h.value:
+            raise RuntimeError(f"rts_compile_scene_encoded failed with {self.rc}")
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().rts_compiled_free(self._h)
+            self._h = None
+
+    def snapshot(self) -> CompiledScene:
+        """Copies of the arrays and scalars as they stand."""
+        return _compiled(self.rc, self._h, keep=True)
+
+    def update_geometry(self, tri_index, p, n, first: int = 0, count: Optional[int] = None) -> int:
+        """tri_index: int array or None (then triangles first .. first + count); p, n: (count, 3, 3).
+        Returns the code (0 or RT_ERR_ARG); the reason is snapshot().err."""
+        idx = None if tri_index is None else np.ascontiguousarray(tri_index, np.int32)
+        if count is None:
+            count = len(idx) if idx is not None else np.asarray(p).reshape(-1, 3, 3).shape[0]
+        arrs = split_vertices(p, n) if p is not None else [None] * 6
+        return lib().rts_compiled_update_geometry(self._h, _ip(idx), int(first), int(count), *[_fp(a) for a in arrs])
+
+    def filter_state(self) -> dict:
+        out = (C.c_double * 5)()
+        _check(lib().rts_compiled_filter_state(self._h, out), "rts_compiled_filter_state")
+        return dict(zip(("s_cap", "sc_cap", "s_max", "sc_max", "c_min"), list(out)))
+
+    def refit_plan(self) -> dict:
+        """leaves (n, 4) int32 {ref, binary parent * 2 + side, 4-wide parent * 4 + slot, 0}; blist / qlist
+        the internal nodes by height with offsets boff / qoff (height h: list[off[h - 1]:off[h]])."""
+        v = RtsRefitPlanView()
+        _check(lib().rts_refit_plan(self._h, C.byref(v)), "rts_refit_plan")
+
+        def take(ptr, n):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        return {"leaves": take(v.leaves, 4 * v.n_leaves).reshape(-1, 4), "blist": take(v.blist, v.n_blist),
+                "boff": take(v.boff, v.n_boff), "qlist": take(v.qlist, v.n_qlist), "qoff": take(v.qoff, v.n_qoff)}
 
 
 def _options(rebuild, greedy, bfs, wide):
