@@ -152,6 +152,15 @@ typedef struct rts_dev_span {
 int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_dev_span* spans, int32_t cap,
                    int32_t* n_spans);
 
+/* The HIP path's render plan (csrc/common/render_plan.h; rt_render_async runs what the same code
+ * decides), for tests only: which kernels one wavefront batch launches.  in = the planner's n_in
+ * inputs in rpl::kInNames order (the context's facts, the call's, the switches; -1 = no override).
+ * out, at most cap values: {batch_cap, serial, pipe_sets, idle_matters, admit_pipe, nf, G,
+ * pix_split}, then per group its rpl::kGroupNames values followed by n_steps steps of
+ * rpl::kStepNames values each.  RTS_ERR_ARG for a wrong n_in, inputs outside the planner's domain
+ * (n_groups 1..4, n_left >= 1, positive kernel constants) or a plan longer than cap. */
+int rts_render_plan(const int64_t* in, int32_t n_in, int64_t* out, int32_t cap, int32_t* n_out);
+
 /* The HIP path's scene compiler (csrc/common/scene_compile.h; rt_set_scene uploads what the same
  * code returns): an rt_scene_soa (rt_abi.h), or the reference's encodings, -> the device arrays
  * and scalars.  A test and tooling interface: it replaces no reference interface.  options = four

@@ -1,8 +1,8 @@
 // rt_dev_report.h — the RT_DEBUG_PASSES reports of the development library (-DRT_DEV): included
 // by rt_render.hip only under RT_DEV, inside its anonymous namespace, after rt_ctx, knob(), HIPCHK,
-// take_event and launch_finish.  Both reports synchronise the group's stream after the launch they
-// describe: measurement aids (tools/pass_counts.py, tools/gpu_run.sh read their text), never part
-// of a timed render.
+// take_event and launch_finish.  The per-pass reports synchronise the group's stream after the
+// launch they describe: measurement aids (tools/pass_counts.py, tools/gpu_run.sh read their text),
+// never part of a timed render.
 
 // RT_DEBUG_PASSES: per-pass report of the COUNT build (syncs after every pass)
 inline bool dev_passes() {
@@ -17,6 +17,28 @@ int dev_wave_log(rt_ctx* c, unsigned long long*& log) {
   if (dev_passes() && !d_wave_log) HIPCHK(c, hipMalloc(&d_wave_log, dev_wave_words(c) * sizeof(unsigned long long)));
   log = dev_passes() ? d_wave_log : nullptr;
   return RT_OK;
+}
+
+// development aid: what the planner (render_plan.h) was given for the batch and what it decided for
+// group g, one line before the group's passes: the inputs, the batch, the group and its steps by
+// name, in kInNames / kGroupNames / kStepNames order (a step's values joined by ',', steps by ';').
+// tests/test_gpu_render_plan.py feeds the inputs back to rts_render_plan and compares.
+void dev_plan_report(const rpl::In& in, const rpl::Batch& B, int g) {
+  int64_t v[rpl::kInCount];
+  static_assert(sizeof(v) == sizeof(in), "In is flat");
+  memcpy(v, &in, sizeof(v));
+  fprintf(stderr, "[rt] plan group %d:", g);
+  for (int k = 0; k < rpl::kInCount; k++) fprintf(stderr, " %s=%lld", rpl::kInNames[k], (long long)v[k]);
+  fprintf(stderr, " nf=%d G=%d pix_split=%d", B.nf, B.G, B.pix_split ? 1 : 0);
+  int64_t gv[rpl::kGroupCount], sv[rpl::kStepCount];
+  rpl::flatten(B.g[g], gv);
+  for (int k = 0; k < rpl::kGroupCount; k++) fprintf(stderr, " %s=%lld", rpl::kGroupNames[k], (long long)gv[k]);
+  fprintf(stderr, " steps=");
+  for (int pass = 0; pass < B.g[g].n_steps; pass++) {
+    rpl::flatten(rpl::step(in.f, in.s, in.c, B.g[g], pass), sv);
+    for (int k = 0; k < rpl::kStepCount; k++) fprintf(stderr, "%s%lld", k ? "," : pass ? ";" : "", (long long)sv[k]);
+  }
+  fprintf(stderr, "\n");
 }
 
 // development aid: the finisher's launch of group g, then its waves (syncs!)

@@ -31,11 +31,9 @@
                          // -0.18, -0.15 / +0.19, +0.22 / -0.03 / -0.04% (profiles/r06_ab_split_passes_C3.log)
 #define RT_SPLIT_PASSES 5
 #endif
-#ifndef RT_SPLIT_CONT_FIRST  // split queues: the continuations' launch first (1) or the shadow rays' (0)
-#define RT_SPLIT_CONT_FIRST 0  // C3 1 vs 0: -0.16% (profiles/r06_ab_split_knobs_C3.log)
-#endif
 #include "scene_compile.h"
 #include "dev_layout.h"
+#include "render_plan.h"
 #include "rt_geometry.h"
 
 using rtd::GNode;
@@ -150,30 +148,6 @@ struct rt_ctx {
     hipEvent_t ev = nullptr;                  // the last upload (the host table is reused after it)
   };
   FrameTable ft[5];
-#ifndef RT_CAM_SHADE  // the bulk camera pass's shade in its own instantiation (wf_shade<..., CAM>)
-#define RT_CAM_SHADE 1
-#endif
-#ifndef RT_CAM_SHARED  // groups of several frames trace each pixel's camera ray once (WFParams::cam_shared)
-#define RT_CAM_SHARED 1
-#endif
-#ifndef RT_CAM_MISS_ONCE  // bulk groups that run the shared camera trace and wf_shade<..., CAM> handle a pixel whose
-                          // camera ray misses once per group, not once per frame (WFParams::cam_miss_once)
-#define RT_CAM_MISS_ONCE 1
-#endif
-#ifndef RT_P1_LEAN  // groups with cam_miss_once and 16-B pass-1 rays in a scene without emissive materials: pass 1
-                    // walks the hit-pixel list (no s5 row, active list or continuation queue out of pass 0:
-                    // WFParams::p1_lean)
-#define RT_P1_LEAN 1
-#endif
-// RT_ROW_COMPACT (rt_wavefront.h): lean groups keep the state of passes >= 2 in dense rows
-// (WFParams::row_compact)
-#ifndef RT_CAM_SHARED_STATIC  // a bulk group's shared camera trace (one ray per work item: a small pass) runs the
-                              // bulk's instantiation (0) or the small passes' (1: static shares, lane quads, every
-                              // claim 64 rays): C3, 2.07 M rays of one 256-frame group standalone 0.299 vs 0.662 ms
-                              // (11 ms per slot before), whole step +0.2% (noise); profiles/r07_passes256_*_C3.log,
-                              // profiles/r07_ab_proc_shared_camera_C3.log
-#define RT_CAM_SHARED_STATIC 0
-#endif
 #ifndef RT_POOL_CHUNK_DEFAULT
 #define RT_POOL_CHUNK_DEFAULT 1024
 #endif
@@ -474,74 +448,54 @@ std::string ovf_layout_error(const rt_ctx* c, int set, unsigned int trace_grid_b
   return std::string();
 }
 
-template <bool COUNT, bool WIDE>
-void launch_trace_w(rt_ctx* c, dim3 grid, const rtd::WFParams& WP, hipStream_t st, bool small) {
-  // pass 1 reads the 16-B rays pass 0 queued (WFState::org) in an instantiation of its own, so the
-  // later passes' kernel carries none of it
-  const bool p1 = !WP.cam_n && WP.pass == 1 && WP.p1_compact;
-  if (small && !COUNT && WIDE) {  // static first shares of mid-size passes
-    if (WP.cam_n)
-      hipLaunchKernelGGL((rtd::wf_trace<false, true, true, true>), grid, dim3(256), c->trace_lds, st, WP);
-    else if (p1)
-      hipLaunchKernelGGL((rtd::wf_trace<false, true, false, true, true>), grid, dim3(256), c->trace_lds, st, WP);
-    else
-      hipLaunchKernelGGL((rtd::wf_trace<false, true, false, true>), grid, dim3(256), c->trace_lds, st, WP);
-    return;
+// One wf_trace launch: rpl::Trace names the instantiation (render_plan.h has what each is for)
+void launch_trace(rt_ctx* c, int trace, dim3 grid, const rtd::WFParams& WP, hipStream_t st) {
+#define RT_TRACE(name, ...) \
+  case rpl::name: hipLaunchKernelGGL((rtd::wf_trace<__VA_ARGS__>), grid, dim3(256), c->trace_lds, st, WP); break
+  switch (trace) {
+    RT_TRACE(CAM_SMALL, false, true, true, true);
+    RT_TRACE(P1_SMALL, false, true, false, true, true);
+    RT_TRACE(REG_SMALL, false, true, false, true);
+    RT_TRACE(P1_SHADOW, false, true, false, false, true, 2);
+    RT_TRACE(P1_CONT_LEAN, false, true, false, false, true, 1, true);
+    RT_TRACE(P1_CONT, false, true, false, false, true, 1);
+    RT_TRACE(SHADOW, false, true, false, false, false, 2);
+    RT_TRACE(CONT, false, true, false, false, false, 1);
+    RT_TRACE(CAM_CW, true, true, true);
+    RT_TRACE(P1_CW, true, true, false, false, true);
+    RT_TRACE(REG_CW, true, true, false);
+    RT_TRACE(CAM_CB, true, false, true);
+    RT_TRACE(P1_CB, true, false, false, false, true);
+    RT_TRACE(REG_CB, true, false, false);
+    RT_TRACE(CAM_W, false, true, true);
+    RT_TRACE(P1_W, false, true, false, false, true);
+    RT_TRACE(REG_W, false, true, false);
+    RT_TRACE(CAM_B, false, false, true);
+    RT_TRACE(P1_B, false, false, false, false, true);
+    RT_TRACE(REG_B, false, false, false);
   }
-  if (WP.split && !WP.cam_n && !COUNT && WIDE) {  // split queues: the shadow rays, then the continuations
-    for (int k = 0; k < 2; k++) {
-      const bool shadow = (k == 0) != (RT_SPLIT_CONT_FIRST != 0);
-      if (p1 && shadow) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, true, 2>), grid, dim3(256), c->trace_lds, st, WP);
-      else if (p1 && WP.p1_lean) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, true, 1, true>), grid, dim3(256), c->trace_lds, st, WP);
-      else if (p1) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, true, 1>), grid, dim3(256), c->trace_lds, st, WP);
-      else if (shadow) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 2>), grid, dim3(256), c->trace_lds, st, WP);
-      else hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 1>), grid, dim3(256), c->trace_lds, st, WP);
-    }
-    return;
+#undef RT_TRACE
+}
+
+// One wf_shade launch: rpl::Shade x the integrator
+void launch_shade(int shade, bool bsdf, dim3 grid, hipStream_t st, const rtd::WFParams& WP) {
+#define RT_SHADE(name, BSDF, ...) \
+  case 2 * rpl::name + BSDF: hipLaunchKernelGGL((rtd::wf_shade<BSDF, __VA_ARGS__>), grid, dim3(256), 0, st, WP); break
+  switch (2 * shade + (bsdf ? 1 : 0)) {
+    RT_SHADE(FUSED, true, true);
+    RT_SHADE(CAM, true, false, rtd::SH_SUB_CAM, true);
+    RT_SHADE(CAM_LEAN, true, false, rtd::SH_SUB_CAM, true, true);
+    RT_SHADE(BULK_LEAN, true, false, rtd::SH_SUB_BULK, false, true);
+    RT_SHADE(BULK, true, false, rtd::SH_SUB_BULK);
+    RT_SHADE(PLAIN, true, false);
+    RT_SHADE(FUSED, false, true);
+    RT_SHADE(CAM, false, false, rtd::SH_SUB_CAM, true);
+    RT_SHADE(CAM_LEAN, false, false, rtd::SH_SUB_CAM, true, true);
+    RT_SHADE(BULK_LEAN, false, false, rtd::SH_SUB_BULK, false, true);
+    RT_SHADE(BULK, false, false, rtd::SH_SUB_BULK);
+    RT_SHADE(PLAIN, false, false);
   }
-  if (WP.cam_n)
-    hipLaunchKernelGGL((rtd::wf_trace<COUNT, WIDE, true>), grid, dim3(256), c->trace_lds, st, WP);
-  else if (p1)
-    hipLaunchKernelGGL((rtd::wf_trace<COUNT, WIDE, false, false, true>), grid, dim3(256), c->trace_lds, st, WP);
-  else
-    hipLaunchKernelGGL((rtd::wf_trace<COUNT, WIDE, false>), grid, dim3(256), c->trace_lds, st, WP);
-}
-
-template <bool COUNT>
-void launch_trace_t(rt_ctx* c, dim3 grid, const rtd::WFParams& WP, hipStream_t st, bool small) {
-  if (c->wide) launch_trace_w<COUNT, true>(c, grid, WP, st, small);
-  else launch_trace_w<COUNT, false>(c, grid, WP, st, small);
-}
-
-// small: a frame group of at most finish_slots path slots (one frame per call), or a bulk
-// group's shared camera trace (one ray per work item)
-void launch_trace(rt_ctx* c, bool count, dim3 grid, const rtd::WFParams& WP, hipStream_t st, bool small) {
-  if (count) launch_trace_t<true>(c, grid, WP, st, small);
-  else launch_trace_t<false>(c, grid, WP, st, small);
-}
-
-// The shade of one pass over `slots` path slots.  fused: one frame per path-state set, the blend
-// inside the shade (WFParams::fuse_blend); bulk: groups above finish_slots, RT_SH_SUB_BULK paths
-// per thread and block-iteration; cam: the camera pass of a bulk group with >= 64 frames
-// (camera-hit records); plain: everything else
-// cam_lean / bulk_lean: pass 0 / pass 1 of a group with WFParams::p1_lean (the LEAN instantiations)
-enum class ShadeKind { plain, bulk, cam, fused, cam_lean, bulk_lean };
-template <bool BSDF>
-void launch_shade_t(ShadeKind kind, dim3 grid, hipStream_t st, const rtd::WFParams& WP) {
-  if (kind == ShadeKind::fused) hipLaunchKernelGGL((rtd::wf_shade<BSDF, true>), grid, dim3(256), 0, st, WP);
-  else if (kind == ShadeKind::cam) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_CAM, true>), grid, dim3(256), 0, st, WP);
-  else if (kind == ShadeKind::cam_lean) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_CAM, true, true>), grid, dim3(256), 0, st, WP);
-  else if (kind == ShadeKind::bulk_lean) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_BULK, false, true>), grid, dim3(256), 0, st, WP);
-  else if (kind == ShadeKind::bulk) hipLaunchKernelGGL((rtd::wf_shade<BSDF, false, rtd::SH_SUB_BULK>), grid, dim3(256), 0, st, WP);
-  else hipLaunchKernelGGL((rtd::wf_shade<BSDF, false>), grid, dim3(256), 0, st, WP);
-}
-void launch_shade(bool bsdf, ShadeKind kind, unsigned int slots, hipStream_t st, const rtd::WFParams& WP) {
-  const unsigned int sub = kind == ShadeKind::cam || kind == ShadeKind::cam_lean    ? (unsigned)rtd::SH_SUB_CAM
-                           : kind == ShadeKind::bulk || kind == ShadeKind::bulk_lean ? (unsigned)rtd::SH_SUB_BULK
-                                                                                      : (unsigned)rtd::SH_SUB;
-  const dim3 grid(std::max(1u, std::min<unsigned int>(4096u, (slots + 256u * sub - 1) / (256u * sub))));
-  if (bsdf) launch_shade_t<true>(kind, grid, st, WP);
-  else launch_shade_t<false>(kind, grid, st, WP);
+#undef RT_SHADE
 }
 
 // wf_finish: one lane per remaining path, trace + shade until the path ends
@@ -1271,6 +1225,7 @@ struct RenderCall {
   std::vector<Frame> frames;       // the traced frames' (loopNum, randOrigin bits), in call order
   int n_traced = 0;                // frames.size()
   int loop_end = 0;                // rt_ctx::loop_num after the call
+  rpl::Switches sw;                // the planner's switches for this call (plan_switches)
   int pipe_sets = 0;
   bool pipe = false, serial = false;
   int pset = 0;                    // pipelined: path-state set, camera table, overflow column, stream aux[1 + pset]
@@ -1299,31 +1254,63 @@ void list_traced_frames(const rt_ctx* c, const rt_frame_params* fp, const float*
   call.loop_end = ln;
 }
 
-// a batch of fewer frames than groups splits by pixels (RT_PIX_SPLIT=0, dev: it stays one group)
-bool pix_split_ok() {
-  static const bool ok = !knob("RT_PIX_SPLIT") || atoi(knob("RT_PIX_SPLIT")) != 0;
-  return ok;
+// The planner's inputs (render_plan.h): the context as it stands (reserve_path_state moves
+// frames_cap and the path state's sizes, so batches copy it again) ...
+rpl::Facts plan_facts(const rt_ctx* c) {
+  auto i64 = [](uint64_t v) { return (int64_t)std::min<uint64_t>(v, (uint64_t)INT64_MAX); };
+  return rpl::Facts{c->n_groups, c->n_valid, c->frames_cap, i64(c->wf_paths), c->finish_pass, c->pipe_finish_pass,
+                    i64(c->finish_slots), c->split_kinds, c->split_passes, c->wide, c->mats_emissive, c->tile_cost_on,
+                    i64(c->wf_hit_cap), i64(c->wf_rows), i64(c->order_head), c->pipe_depth, i64(c->pipe_nomem_slots),
+                    c->n_cus, c->trace_bpc0, c->trace_bpc, c->finish_bpc, c->pipe_finish_bpc, rtd::SH_SUB, rtd::SH_SUB_CAM,
+                    rtd::SH_SUB_BULK, (int64_t)rtd::kP1SampleEvery};
+}
+// ... and the switches: the release defaults, in the development library with the A/B settings of
+// this call's environment (the tests flip them between calls)
+rpl::Switches plan_switches(const rt_ctx* c) {
+  rpl::Switches S;
+#ifdef RT_DEV
+  auto off = [](const char* name, int64_t& v) {  // (A/B: these only switch off)
+    if (const char* e = knob(name)) v = v && atoi(e) != 0;
+  };
+  off("RT_PIX_SPLIT", S.pix_split);
+  off("RT_CAM_SHARED", S.cam_shared);
+  off("RT_CAM_MISS_ONCE", S.cam_miss_once);
+  off("RT_P1_LEAN", S.p1_lean);
+  off("RT_ROW_COMPACT", S.row_compact);
+  if (const char* e = knob("RT_CAM_SHARED_STATIC")) S.cam_shared_static = atoi(e) != 0;
+  if (const char* e = knob("RT_GROUP_SPLIT"))  // group 0's share of the work items, in whole blocks
+    S.group_head = (int64_t)std::min((size_t)c->n_valid, ((size_t)((double)c->n_valid * atof(e)) + 63) / 64 * 64);
+  for (int g = 0; g < rpl::kMaxGroups; g++) {
+    char kn[32];
+    snprintf(kn, sizeof(kn), "RT_FINISH_PASS_G%d", g);
+    if (const char* e = knob(kn)) S.finish_pass_g[g] = std::max(0, atoi(e));
+  }
+  if (const char* e = knob("RT_ROW_CAP")) S.row_cap = (int64_t)std::min<uint64_t>(strtoull(e, nullptr, 10), (uint64_t)INT64_MAX);  // (tests: rows)
+#else
+  (void)c;
+#endif
+  return S;
+}
+rpl::Call plan_call(const rt_frame_params* fp, const RenderCall& call, int n_left) {
+  return rpl::Call{fp->flags, fp->enable_bsdf, fp->max_bounce, n_left, 0, call.pipe, call.pset};
 }
 
-// a pipelined call (rt_set_pipeline): see rt_ctx::pipe_depth.  One-frame calls, and calls of
-// one batch (at most frames_cap frames) whose whole path state fits in each set.
+// a pipelined call (rt_set_pipeline): see rt_ctx::pipe_depth and rpl::admit_pipe; here only the
+// look at the streams it asks for
 void admit_pipeline(rt_ctx* c, const rt_frame_params* fp, RenderCall& call) {
-  const int n = call.n_traced;
-  const size_t nv = std::max<size_t>(1, (size_t)c->n_valid);
-  call.pipe_sets = std::min(c->pipe_depth, c->n_groups);
-  call.serial = (fp->flags & RT_FLAG_SERIAL) != 0 && !(fp->flags & RT_FLAG_MEGAKERNEL);
-  call.pipe = call.pipe_sets >= 2 && !(fp->flags & RT_FLAG_MEGAKERNEL) && !call.serial && n > 0 &&
-              c->n_valid >= 64 * c->n_groups && !c->tile_cost_on &&
-              (n < c->n_groups || (n <= c->frames_cap && (size_t)n * nv < c->pipe_nomem_slots));
-  if (call.pipe && n < c->n_groups && pix_split_ok()) {
-    // a one-frame call with no call in flight has nothing to overlap: the pixel-split groups
-    // (plan_groups) have the lower latency (C4 1080p 5.6 vs 6.8 ms synchronised)
+  const rpl::Facts F = plan_facts(c);
+  rpl::Call C = plan_call(fp, call, call.n_traced);
+  call.sw = plan_switches(c);
+  call.pipe_sets = rpl::pipe_sets(F);
+  call.serial = rpl::serial(C);
+  if (rpl::idle_matters(F, call.sw, C)) {
     bool idle = !(c->batch_done && hipEventQuery(c->batch_done) != hipSuccess);
     for (int q = 0; q < call.pipe_sets && idle; q++)
       if (c->set_free[q] && hipEventQuery(c->set_free[q]) != hipSuccess) idle = false;
     (void)hipGetLastError();  // (hipErrorNotReady is a status, not an error)
-    if (idle) call.pipe = false;
+    C.idle = idle;
   }
+  call.pipe = rpl::admit_pipe(F, call.sw, C);
 }
 
 // Path state for the call's batches (it only grows) and the frame groups' streams
@@ -1532,71 +1519,49 @@ int megakernel_batch(rt_ctx* c, const rt_frame_params* fp, const KParams& P) {
   return RT_OK;
 }
 
-// The groups of one wavefront batch (plan_groups), each with its own path state and stream
+// One wavefront batch: what the planner decided from `in` (B: the groups, each with its own path
+// state and stream) and the kernel parameters and streams that go with it (plan_groups)
 struct GroupPlan {
-  int G = 1;
-  bool pix_split = false;
+  rpl::In in;
+  rpl::Batch B;
   rtd::WFParams WG[rt_ctx::MAX_GROUPS];
   hipStream_t sg[rt_ctx::MAX_GROUPS];
-  unsigned int slots_g[rt_ctx::MAX_GROUPS];
-  int split_g[rt_ctx::MAX_GROUPS] = {};
   float4* cam = nullptr;           // this call's camera table (wf_camera writes it, every group reads it)
   hipEvent_t prev_blend = nullptr; // after the previous frame group's blend (blend_and_join)
 };
+static_assert(rpl::kMaxGroups == rt_ctx::MAX_GROUPS, "the planner's groups are rt_ctx's");
 
-// Split the batch (P: P.n_frames frames) into frame groups (frames [f0, f1) each), one stream per
-// group; a batch of fewer frames than groups (one frame per call: the reference's own usage) is
-// split by pixels instead (work items [w0, w1) each, all frames), so the groups' latency-bound
-// late passes still overlap each other
-int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, const KParams& P, GroupPlan& plan) {
-  const bool pipe = call.pipe, count = (fp->flags & RT_FLAG_COUNT_VISITS) != 0;
-  const int nf = P.n_frames;
-  const bool pix_split = !pipe && !call.serial && pix_split_ok() && nf < c->n_groups && c->n_valid >= 64 * c->n_groups && !c->tile_cost_on;
-  const int G = (pipe || call.serial) ? 1 : pix_split ? c->n_groups : std::min(c->n_groups, nf);
-  plan.G = G;
-  plan.pix_split = pix_split;
+// The batch's groups as rpl::plan_batch cuts them (P: the batch's frames), the pointers of their
+// kernel parameters, and the overflow column's layout check
+int plan_groups(rt_ctx* c, const RenderCall& call, const KParams& P, GroupPlan& plan) {
+  const rpl::Batch& B = plan.B = rpl::plan_batch(plan.in.f, plan.in.s, plan.in.c);
   const unsigned int trace_grid = (unsigned)(c->n_cus * std::max(c->trace_bpc, c->trace_bpc0));
   unsigned long long* d_wave_log = nullptr;  // COUNT builds (RT_DEBUG_PASSES)
 #ifdef RT_DEV
   if (int rc = dev_wave_log(c, d_wave_log)) return rc;
 #endif
   const size_t ovf_group = c->stack_ovf_bytes / sizeof(int2) / (size_t)c->n_groups;
-  // pixel ranges of the groups: even, or after rt_order_work the costly head as group 0 and
-  // the rest split evenly (dev: RT_GROUP_SPLIT = group 0's share)
-  size_t b0 = std::min(c->order_head, (size_t)c->n_valid);
-#ifdef RT_DEV
-  if (const char* e = knob("RT_GROUP_SPLIT")) b0 = std::min((size_t)c->n_valid, ((size_t)((double)c->n_valid * atof(e)) + 63) / 64 * 64);
-#endif
-  auto wbound = [&](int g) -> unsigned int {
-    if (g <= 0) return 0u;
-    if (g >= G) return (unsigned)c->n_valid;
-    if (b0 > 0 && G > 1) return (unsigned)(b0 + ((size_t)c->n_valid - b0) * (g - 1) / (G - 1));
-    return (unsigned)((size_t)c->n_valid * g / G);
-  };
   // the call's camera directions and camera hit points (WFState::org): one table of each per set
   const dvl::CameraTable CT = dvl::camera_table((size_t)c->n_valid, (size_t)c->cam_sets);
-  const size_t cam_set = pipe ? (size_t)call.pset : 0;
+  const size_t cam_set = call.pipe ? (size_t)call.pset : 0;
   plan.cam = c->wf.cam + CT.dir(cam_set).off;
   float4* const org = c->wf.cam + CT.org(cam_set).off;
-  for (int g = 0; g < G; g++) {
-    const int f0 = pix_split ? 0 : g * nf / G, f1 = pix_split ? nf : (g + 1) * nf / G;
-    const unsigned int w0 = pix_split ? wbound(g) : 0u;
-    const unsigned int w1 = pix_split ? wbound(g + 1) : (unsigned)c->n_valid;
+  for (int g = 0; g < B.G; g++) {
+    const rpl::Group& G = B.g[g];
     rtd::WFParams& WP = plan.WG[g];
     WP.K = P;
-    WP.K.loop_num = P.loop_num + f0;
-    WP.K.rand_origin = P.rand_origin + f0;
-    WP.K.sobol = P.sobol + 4 * f0;
-    WP.K.blend_w = P.blend_w + f0;
-    WP.K.n_frames = f1 - f0;
-    WP.K.n_work = w1 - w0;
+    WP.K.loop_num = P.loop_num + G.f0;
+    WP.K.rand_origin = P.rand_origin + G.f0;
+    WP.K.sobol = P.sobol + 4 * G.f0;
+    WP.K.blend_w = P.blend_w + G.f0;
+    WP.K.n_frames = G.f1 - G.f0;
+    WP.K.n_work = G.w1 - G.w0;
     WP.K.lds_entries = c->trace_lds_entries;
     WP.K.pool_chunk = c->pool_chunk;
-    const int set = pipe ? call.pset : g;  // path-state set, overflow column, stream
-    WP.K.stack_ovf = c->d_stack_ovf ? c->d_stack_ovf + (size_t)set * ovf_group : nullptr;
+    WP.K.stack_ovf = c->d_stack_ovf ? c->d_stack_ovf + (size_t)G.set * ovf_group : nullptr;
     WP.K.ovf_lanes = trace_grid * 256u;
     {
-      const std::string e = ovf_layout_error(c, set, trace_grid);
+      const std::string e = ovf_layout_error(c, G.set, trace_grid);
       if (!e.empty()) return fail(c, RT_ERR_STATE, e);
     }
     WP.K.wave_log = d_wave_log;
@@ -1605,31 +1570,29 @@ int plan_groups(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, co
     // on a few lines would set the pass times)
     if (d_wave_log && knob("RT_DEBUG_WAVES_ONLY")) WP.K.flags |= rtd::kFlagNoRayHist;
 #endif
-    WP.S = c->wfg[set];
-    WP.S.pix_xy = c->wf.pix_xy + w0;
-    WP.S.pix_acc = c->wf.pix_acc + w0;
-    WP.S.cam = plan.cam + w0;
-    WP.S.org = org + w0;
-    WP.n_frames = f1 - f0;
+    WP.S = c->wfg[G.set];
+    WP.S.pix_xy = c->wf.pix_xy + G.w0;
+    WP.S.pix_acc = c->wf.pix_acc + G.w0;
+    WP.S.cam = plan.cam + G.w0;
+    WP.S.org = org + G.w0;
+    WP.A = c->wfa[G.set];  // (the arena's own arrays; the per-call tables as S)
+    WP.A.pix_xy = WP.S.pix_xy;
+    WP.A.pix_acc = WP.S.pix_acc;
+    WP.A.cam = WP.S.cam;
+    WP.A.org = WP.S.org;
+    // the group's flags: those that wf_cam_classify and the kernels after it read enter after
+    // pass 0's trace (run_group_passes)
+    WP.n_frames = G.f1 - G.f0;
     WP.pass = 0;
     WP.cam_n = 0u;
     WP.cam_shared = 0;
     WP.cam_miss_once = 0;
     WP.p1_lean = 0;
-    WP.A = c->wfa[set];  // (the arena's own arrays; the per-call tables as S)
-    WP.A.pix_xy = WP.S.pix_xy;
-    WP.A.pix_acc = WP.S.pix_acc;
-    WP.A.cam = WP.S.cam;
-    WP.A.org = WP.S.org;
     WP.row_compact = 0;
     WP.row_cap = 0u;
-    // (not for frame groups of one frame each: their blends must run in frame order)
-    WP.fuse_blend = (!pipe && WP.n_frames == 1 && (pix_split || G == 1) && !count) ? 1 : 0;
-    plan.slots_g[g] = (unsigned)(f1 - f0) * (w1 - w0);
-    // bulk groups (the wf_shade<..., SH_SUB_BULK / CAM> launches) queue the two ray kinds apart
-    // (per pass in run_group_passes: passes 1 .. split_passes)
-    plan.split_g[g] = (c->split_kinds && c->wide && !count && !c->tile_cost_on && plan.slots_g[g] > c->finish_slots && !WP.fuse_blend) ? 1 : 0;
-    plan.sg[g] = pipe ? call.ps : g == 0 ? c->stream : c->aux[g];
+    WP.fuse_blend = G.fuse_blend ? 1 : 0;
+    WP.p1_compact = G.p1_compact ? 1 : 0;
+    plan.sg[g] = G.stream == 0 ? c->stream : c->aux[G.stream];
   }
   return RT_OK;
 }
@@ -1645,73 +1608,52 @@ int launch_camera_and_fork(rt_ctx* c, const RenderCall& call, GroupPlan& plan) {
   WC.S.cam = plan.cam;
   rtd::GroupCounters Z;
   memset(&Z, 0, sizeof(Z));
-  Z.n = plan.G;
-  for (int g = 0; g < plan.G; g++) Z.cnt[g] = plan.WG[g].S.cnt;
+  Z.n = plan.B.G;
+  for (int g = 0; g < plan.B.G; g++) Z.cnt[g] = plan.WG[g].S.cnt;
   hipLaunchKernelGGL(rtd::wf_camera, dim3(std::max(1u, std::min<unsigned int>(2048u, ((unsigned)c->n_valid + 255) / 256))),
                      dim3(256), 0, call.ps, WC, Z);
   HIPCHK(c, hipGetLastError());
-  if (plan.G > 1) {
+  if (plan.B.G > 1) {
     hipEvent_t es;
     TAKE_EVENT(c, es);
     HIPCHK(c, hipEventRecord(es, c->stream));
-    for (int g = 1; g < plan.G; g++) HIPCHK(c, hipStreamWaitEvent(plan.sg[g], es, 0));
+    for (int g = 1; g < plan.B.G; g++) HIPCHK(c, hipStreamWaitEvent(plan.sg[g], es, 0));
     c->event_pool.push_back(es);  // reusable once the waits are enqueued
   }
   return RT_OK;
 }
 
-// Group g's wavefront passes on its stream: trace + shade per pass, or the finisher from fin_pass
-int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& call, GroupPlan& plan, int g) {
+// Group g's wavefront passes on its stream, as rpl::step lists them: trace(s) + shade per pass, or
+// the finisher as the last step
+int run_group_passes(rt_ctx* c, GroupPlan& plan, int g) {
+  const rpl::In& in = plan.in;
+  const rpl::Group& G = plan.B.g[g];
   rtd::WFParams& WP = plan.WG[g];  // (its pass counters were zeroed by wf_camera)
   const hipStream_t st = plan.sg[g];
-  const unsigned int slots = plan.slots_g[g];
-  const bool count = (fp->flags & RT_FLAG_COUNT_VISITS) != 0, bsdf = fp->enable_bsdf != 0;
-  const int last_pass = std::max(0, fp->max_bounce);
-  // small groups (one frame per call) end their paths in wf_finish after pass finish_pass-1
-  int fin_pass = (call.pipe && c->pipe_finish_pass >= 0) ? c->pipe_finish_pass : c->finish_pass;
+  const bool bsdf = in.c.enable_bsdf != 0;
 #ifdef RT_DEV
-  {
-    char kn[32];
-    snprintf(kn, sizeof(kn), "RT_FINISH_PASS_G%d", g);
-    if (const char* e = knob(kn)) fin_pass = std::max(0, atoi(e));
-  }
+  if (dev_passes()) dev_plan_report(plan.in, plan.B, g);
 #endif
-  const bool finish = !count && !c->tile_cost_on && !(fp->flags & RT_FLAG_NO_FINISH) &&
-                      fin_pass >= 1 && fin_pass <= last_pass &&
-                      ((fp->flags & RT_FLAG_FINISH) || slots <= c->finish_slots);
-  // pass 0 queues 16-B rays (WFState::org) unless the finisher takes them over at pass 1
-  WP.p1_compact = (finish && fin_pass <= 1) ? 0 : 1;
-  for (int pass = 0; pass <= last_pass; pass++) {
+  for (int pass = 0; pass < G.n_steps; pass++) {
+    const rpl::Step s = rpl::step(in.f, in.s, in.c, G, pass);
     WP.pass = pass;
-    WP.split = (plan.split_g[g] && pass >= 1 && pass <= c->split_passes) ? 1 : 0;
-    WP.split_out = (plan.split_g[g] && pass + 1 <= c->split_passes) ? 1 : 0;
-    if (finish && pass == fin_pass) {
-      const dim3 fgrid((unsigned)(c->n_cus * (call.pipe ? c->pipe_finish_bpc : c->finish_bpc)));
+    WP.split = s.split ? 1 : 0;
+    WP.split_out = s.split_out ? 1 : 0;
+    if (s.finisher) {
 #ifdef RT_DEV
-      if (dev_passes()) return dev_finish_report(c, bsdf, fgrid, st, WP, g, pass);
+      if (dev_passes()) return dev_finish_report(c, bsdf, dim3(s.fgrid), st, WP, g, pass);
 #endif
-      launch_finish(c, bsdf, fgrid, st, WP);
+      launch_finish(c, bsdf, dim3(s.fgrid), st, WP);
       HIPCHK(c, hipGetLastError());
       break;
     }
-    // pass 0's camera paths are implicit (wf_trace / wf_shade generate them)
-    WP.cam_n = pass == 0 ? slots : 0u;
-    // a group of several frames traces each work item's camera ray once and every frame's shade
-    // reads that result.  The counting runs (RT_FLAG_COUNT_VISITS, and with it the rt_tile_costs /
-    // rt_order_work probes and the counting per-pass reports) keep one traversal per path slot:
-    // their counters are the steps of the rays counted in rt_stats.rays, and the tile balance is
-    // calibrated on them.
-    bool cam_shared = RT_CAM_SHARED && pass == 0 && WP.n_frames > 1 && !count && !c->tile_cost_on;
-    bool cam_static = RT_CAM_SHARED_STATIC != 0;
-    if (const char* e = knob("RT_CAM_SHARED")) cam_shared = cam_shared && atoi(e) != 0;  // (A/B)
-    if (const char* e = knob("RT_CAM_SHARED_STATIC")) cam_static = atoi(e) != 0;           // (A/B)
-    WP.cam_shared = cam_shared ? 1 : 0;
+    WP.cam_n = s.cam_n;
+    WP.cam_shared = s.cam_shared ? 1 : 0;
     hipEvent_t t0, t1;
     TAKE_EVENT(c, t0);
     TAKE_EVENT(c, t1);
     HIPCHK(c, hipEventRecord(t0, st));
-    launch_trace(c, count, dim3((unsigned)(c->n_cus * (pass == 0 ? c->trace_bpc0 : c->trace_bpc))), WP, st,
-                 slots <= c->finish_slots || (cam_shared && cam_static));
+    for (int k = 0; k < s.n_trace; k++) launch_trace(c, s.trace[k], dim3(s.trace_grid), WP, st);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, st));
     c->trace_events.push_back({t0, t1, c->launches});
@@ -1719,48 +1661,22 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
 #ifdef RT_DEV
     if (dev_passes()) if (int rc = dev_pass_report(c, st, WP, g, pass, t0, t1)) return rc;
 #endif
-    const bool bulk = slots > c->finish_slots && !WP.fuse_blend;
-    const bool cam = RT_CAM_SHADE && bulk && WP.cam_n && WP.n_frames >= 64;
-    if (pass == 0) {
-      // the groups that run both the shared camera trace and the CAM shade: miss pixels get their
-      // record and the hit pixels their list before the shade (wf_cam_classify: neither a trace nor
-      // a render launch in rt_stats); the flag stays set for the group's wf_blend
-      bool miss_once = RT_CAM_MISS_ONCE && cam && cam_shared && WP.K.n_work <= c->wf_hit_cap;
-      if (const char* e = knob("RT_CAM_MISS_ONCE")) miss_once = miss_once && atoi(e) != 0;  // (A/B)
-      WP.cam_miss_once = miss_once ? 1 : 0;
-      // the lean pass-0 -> pass-1 state: pass 1 exists, reads 16-B rays and split queues, and no
-      // camera hit can be emissive
-      bool lean = RT_P1_LEAN && miss_once && WP.p1_compact && last_pass >= 1 && WP.split_out && !c->mats_emissive;
-      if (const char* e = knob("RT_P1_LEAN")) lean = lean && atoi(e) != 0;  // (A/B)
-      WP.p1_lean = lean ? 1 : 0;
-      // lean groups move the state of passes >= 2 to the row arena when pass 1's continuation hits
-      // fit a quarter of the group's slots (decided on the device: rtd::rows_on)
-      // (not when wf_finish ends the group's paths: it reads the slot-indexed state)
-      bool rowc = RT_ROW_COMPACT && lean && !finish;
-      if (const char* e = knob("RT_ROW_COMPACT")) rowc = rowc && atoi(e) != 0;  // (A/B)
-      size_t cap = std::min(dvl::arena_rows(slots), c->wf_rows);
-      if (const char* e = knob("RT_ROW_CAP")) cap = std::min(cap, (size_t)strtoull(e, nullptr, 10));  // (tests: rows)
-      WP.row_compact = rowc ? 1 : 0;
-      WP.row_cap = (unsigned int)cap;
-      if (miss_once) {
-        // (two blocks per CU: few waves, so few atomics on the list's counter)
-        hipLaunchKernelGGL(rtd::wf_cam_classify, dim3(std::max(1u, std::min<unsigned int>(2u * (unsigned)c->n_cus, (WP.K.n_work + 255u) / 256u))),
-                           dim3(256), 0, st, WP);
-        HIPCHK(c, hipGetLastError());
-      }
+    if (pass == 0) {  // from here to the group's wf_blend
+      WP.cam_miss_once = G.cam_miss_once ? 1 : 0;
+      WP.p1_lean = G.p1_lean ? 1 : 0;
+      WP.row_compact = G.row_compact ? 1 : 0;
+      WP.row_cap = G.row_cap;
     }
-    const bool lean0 = WP.p1_lean && pass == 0, lean1 = WP.p1_lean && pass == 1;
-    if (lean1 && WP.row_compact) {  // the hits the shade will number with rows (rtd::rows_on reads the count)
-      const unsigned int items = (unsigned)std::min<size_t>(slots, (size_t)WP.K.n_work * (size_t)WP.n_frames);
-      const unsigned int runs = (items + 255u) / 256u;
-      hipLaunchKernelGGL(rtd::wf_p1_count<true>, dim3(std::max(1u, std::min<unsigned int>(8u * (unsigned)c->n_cus, runs / rtd::kP1SampleEvery + 1u))),
-                         dim3(256), 0, st, WP);
-      hipLaunchKernelGGL(rtd::wf_p1_count<false>, dim3(std::max(1u, std::min<unsigned int>(8u * (unsigned)c->n_cus, runs))), dim3(256), 0, st, WP);
+    if (s.classify) {  // (neither a trace nor a render launch in rt_stats)
+      hipLaunchKernelGGL(rtd::wf_cam_classify, dim3(s.classify_grid), dim3(256), 0, st, WP);
       HIPCHK(c, hipGetLastError());
     }
-    launch_shade(bsdf, WP.fuse_blend ? ShadeKind::fused : lean0 ? ShadeKind::cam_lean : cam ? ShadeKind::cam
-                       : lean1 ? ShadeKind::bulk_lean : bulk ? ShadeKind::bulk : ShadeKind::plain,
-                 slots, st, WP);
+    if (s.p1_count) {
+      hipLaunchKernelGGL(rtd::wf_p1_count<true>, dim3(s.p1_grid[0]), dim3(256), 0, st, WP);
+      hipLaunchKernelGGL(rtd::wf_p1_count<false>, dim3(s.p1_grid[1]), dim3(256), 0, st, WP);
+      HIPCHK(c, hipGetLastError());
+    }
+    launch_shade(s.shade, bsdf, dim3(s.shade_grid), st, WP);
     HIPCHK(c, hipGetLastError());
 #ifdef RT_DEV
     if (dev_passes() && pass == 1) if (int rc = dev_rows_report(c, st, WP)) return rc;
@@ -1773,7 +1689,7 @@ int run_group_passes(rt_ctx* c, const rt_frame_params* fp, const RenderCall& cal
 // the groups
 int blend_and_join(rt_ctx* c, RenderCall& call, GroupPlan& plan, int g) {
   const hipStream_t st = plan.sg[g];
-  const int G = plan.G;
+  const int G = plan.B.G;
   // progressive blend in frame order: group g after group g-1 (pixel groups blend
   // disjoint pixels: no order between them)
   if (plan.prev_blend) {
@@ -1786,19 +1702,19 @@ int blend_and_join(rt_ctx* c, RenderCall& call, GroupPlan& plan, int g) {
     c->event_pool.push_back(call.e_entry);  // reusable once the wait is enqueued
     call.e_entry = nullptr;
   }
-  if (!plan.WG[g].fuse_blend) {
+  if (plan.B.g[g].blend) {
     hipLaunchKernelGGL(rtd::wf_blend, dim3(std::max(1u, std::min<unsigned int>(2048u, ((unsigned)c->n_valid + 255) / 256))),
                        dim3(256), 0, st, plan.WG[g]);
     HIPCHK(c, hipGetLastError());
   }
-  if (!plan.pix_split && g + 1 < G) {
+  if (!plan.B.pix_split && g + 1 < G) {
     TAKE_EVENT(c, plan.prev_blend);
     HIPCHK(c, hipEventRecord(plan.prev_blend, st));
   }
   if (g + 1 < G) return RT_OK;
   // the caller's stream joins the last group (frame groups finish in order through their
   // blends) or every group (pixel groups)
-  for (int j = plan.pix_split ? 1 : G - 1; j < G && G > 1; j++) {
+  for (int j = plan.B.pix_split ? 1 : G - 1; j < G && G > 1; j++) {
     hipEvent_t ej;
     TAKE_EVENT(c, ej);
     HIPCHK(c, hipEventRecord(ej, plan.sg[j]));
@@ -1851,13 +1767,10 @@ int rt_render_async(rt_ctx* c, const rt_frame_params* fp, const float* rand_orig
   if (int rc = bind_light_table(c, fp, call)) return rc;
   KParams P;
   fill_kparams(c, fp, call, P);
-  const size_t nv = std::max<size_t>(1, (size_t)c->n_valid);
   for (int done = 0, nf = 0; done < call.n_traced; done += nf) {
-    // RT_FLAG_SERIAL: one frame group per batch, as many frames as one group's path state holds
-    const int cap = mega ? RT_MAX_FRAMES_PER_LAUNCH
-                    : call.serial ? (int)std::max<size_t>(1, std::min<size_t>((size_t)c->frames_cap, c->wf_paths / nv))
-                                  : c->frames_cap;
-    nf = std::min(cap, call.n_traced - done);
+    GroupPlan plan;
+    plan.in = rpl::In{plan_facts(c), plan_call(fp, call, call.n_traced - done), call.sw};
+    nf = std::min(rpl::batch_cap(plan.in.f, plan.in.c), call.n_traced - done);
     P.loop_num = call.d_loop + done;
     P.rand_origin = call.d_ro + done;
     P.sobol = call.d_sobol + 4 * (size_t)done;
@@ -1871,11 +1784,10 @@ int rt_render_async(rt_ctx* c, const rt_frame_params* fp, const float* rand_orig
     if (mega) {
       if (int rc = megakernel_batch(c, fp, P)) return rc;
     } else {
-      GroupPlan plan;
-      if (int rc = plan_groups(c, fp, call, P, plan)) return rc;
+      if (int rc = plan_groups(c, call, P, plan)) return rc;
       if (int rc = launch_camera_and_fork(c, call, plan)) return rc;
-      for (int g = 0; g < plan.G; g++) {
-        if (int rc = run_group_passes(c, fp, call, plan, g)) return rc;
+      for (int g = 0; g < plan.B.G; g++) {
+        if (int rc = run_group_passes(c, plan, g)) return rc;
         if (int rc = blend_and_join(c, call, plan, g)) return rc;
       }
     }
@@ -2429,9 +2341,7 @@ int query_chunk_launch(rt_ctx* c, const rtd::WFParams& WP, const float* rays_dev
                      origin_bound, any ? 1 : 0, any_kernel ? rtd::cqs(0) : rtd::cq(0));
   HIPCHK(c, hipGetLastError());
   const dim3 grid((unsigned)(c->n_cus * c->trace_bpc));
-  if (any_kernel) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 2>), grid, dim3(256), c->trace_lds, c->stream, WP);
-  else if (c->wide) hipLaunchKernelGGL((rtd::wf_trace<false, true, false, false, false, 1>), grid, dim3(256), c->trace_lds, c->stream, WP);
-  else hipLaunchKernelGGL((rtd::wf_trace<false, false, false>), grid, dim3(256), c->trace_lds, c->stream, WP);
+  launch_trace(c, any_kernel ? rpl::SHADOW : c->wide ? rpl::CONT : rpl::REG_B, grid, WP, c->stream);
   HIPCHK(c, hipGetLastError());
   if (any) hipLaunchKernelGGL(rtd::wf_query_resolve_any, query_grid(n), dim3(256), 0, c->stream, WP.S, (unsigned)n, (int*)out_dev);
   else hipLaunchKernelGGL(rtd::wf_query_resolve<false>, query_grid(n), dim3(256), 0, c->stream, WP, (unsigned)n, (float4*)out_dev);
@@ -2518,8 +2428,7 @@ int first_hit_launch(rt_ctx* c, const rt_frame_params* fp, float4* hits_dev) {
     hipLaunchKernelGGL(rtd::wf_camera, query_grid(n), dim3(256), 0, c->stream, WP, Z);
     HIPCHK(c, hipGetLastError());
     const dim3 grid((unsigned)(c->n_cus * c->trace_bpc0));
-    if (c->wide) hipLaunchKernelGGL((rtd::wf_trace<false, true, true>), grid, dim3(256), c->trace_lds, c->stream, WP);
-    else hipLaunchKernelGGL((rtd::wf_trace<false, false, true>), grid, dim3(256), c->trace_lds, c->stream, WP);
+    launch_trace(c, c->wide ? rpl::CAM_W : rpl::CAM_B, grid, WP, c->stream);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(rtd::wf_query_resolve<true>, query_grid(n), dim3(256), 0, c->stream, WP, n, hits_dev);
     HIPCHK(c, hipGetLastError());

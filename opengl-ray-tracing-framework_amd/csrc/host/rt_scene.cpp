@@ -8,6 +8,7 @@
 // -ffp-contract=off (no FMA contraction, as the reference's x86-64 SSE build).
 #include "rt_scene.h"
 #include "dev_layout.h"
+#include "render_plan.h"
 #include "scene_compile.h"
 #include "tri_filter.h"
 
@@ -1372,6 +1373,38 @@ int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_
   }
   *n_spans = k;
   return fits ? RTS_OK : RTS_ERR_ARG;
+}
+
+int rts_render_plan(const int64_t* in, int32_t n_in, int64_t* out, int32_t cap, int32_t* n_out) {
+  if (!in || !out || !n_out || cap < 0 || n_in != rpl::kInCount) return RTS_ERR_ARG;
+  rpl::In I;
+  memcpy(static_cast<void*>(&I), in, sizeof(I));  // (trivially copyable: the switches only have defaults)
+  const rpl::Facts& F = I.f;
+  if (F.n_groups < 1 || F.n_groups > rpl::kMaxGroups || F.n_valid < 0 || F.n_valid > UINT32_MAX || F.frames_cap < 1 ||
+      F.n_cus < 1 || F.sh_sub < 1 || F.sh_sub_cam < 1 || F.sh_sub_bulk < 1 || F.p1_sample_every < 1 || I.c.n_left < 1 ||
+      I.c.pset < 0 || I.c.pset + 1 >= rpl::kMaxGroups)
+    return RTS_ERR_ARG;
+  int32_t k = 0;
+  auto put = [&](const int64_t* v, int n) {
+    for (int i = 0; i < n; i++, k++)
+      if (k < cap) out[k] = v[i];
+  };
+  const rpl::Batch B = rpl::plan_batch(F, I.s, I.c);
+  const int64_t head[8] = {rpl::batch_cap(F, I.c), rpl::serial(I.c), rpl::pipe_sets(F), rpl::idle_matters(F, I.s, I.c),
+                           rpl::admit_pipe(F, I.s, I.c), B.nf, B.G, B.pix_split};
+  put(head, 8);
+  for (int g = 0; g < B.G; g++) {
+    int64_t gv[rpl::kGroupCount], sv[rpl::kStepCount];
+    rpl::flatten(B.g[g], gv);
+    put(gv, rpl::kGroupCount);
+    for (int pass = 0; pass < B.g[g].n_steps && k <= cap; pass++) {
+      rpl::flatten(rpl::step(F, I.s, I.c, B.g[g], pass), sv);
+      put(sv, rpl::kStepCount);
+    }
+    if (k > cap) return RTS_ERR_ARG;
+  }
+  *n_out = k;
+  return RTS_OK;
 }
 
 // ---- the HIP path's scene compiler (csrc/common/scene_compile.h), for tests and tooling

@@ -145,6 +145,7 @@ def lib() -> C.CDLL:
         L.rts_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
         L.rts_tri_filter.argtypes = [_f32p, C.c_int, _f32p, C.POINTER(C.c_double), _i32p]
         L.rts_dev_layout.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_int32, _i32p]
+        L.rts_render_plan.argtypes = [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _i32p]
         L.rts_compile_scene.argtypes = [vp, _i32p, C.POINTER(vp)]
         L.rts_compile_scene_encoded.argtypes = [_f32p, C.c_int32, _f32p, C.c_int32, _i32p, C.POINTER(vp)]
         L.rts_compiled_get.argtypes = [vp, C.POINTER(RtsCompiledView)]
@@ -405,6 +406,60 @@ def dev_layout(kind: str, n: int, m: int = 1):
     assert len(names) == cnt.value, (kind, len(names), cnt.value)
     return list(scalars), [dict(name=nm, off=s.off, bytes=s.bytes, host=s.host, live=s.live)
                            for nm, s in zip(names, spans)]
+
+
+# rts_render_plan (csrc/common/render_plan.h): the names of its inputs (rpl::kInNames), of a group's
+# and a step's values (kGroupNames, kStepNames) and of its enumerators (rpl::Trace, rpl::Shade)
+PLAN_INPUTS = (
+    "n_groups", "n_valid", "frames_cap", "wf_paths", "finish_pass", "pipe_finish_pass", "finish_slots", "split_kinds",
+    "split_passes", "wide", "mats_emissive", "tile_cost_on", "wf_hit_cap", "wf_rows", "order_head", "pipe_depth",
+    "pipe_nomem_slots", "n_cus", "trace_bpc0", "trace_bpc", "finish_bpc", "pipe_finish_bpc", "sh_sub", "sh_sub_cam",
+    "sh_sub_bulk", "p1_sample_every",
+    "flags", "enable_bsdf", "max_bounce", "n_left", "idle", "pipe", "pset",
+    "sw_cam_shade", "sw_cam_shared", "sw_cam_shared_static", "sw_cam_miss_once", "sw_p1_lean", "sw_row_compact",
+    "sw_split_cont_first", "sw_pix_split", "sw_group_head", "sw_finish_pass_g0", "sw_finish_pass_g1", "sw_finish_pass_g2",
+    "sw_finish_pass_g3", "sw_row_cap")
+PLAN_HEAD = ("batch_cap", "serial", "pipe_sets", "idle_matters", "admit_pipe", "nf", "G", "pix_split")
+PLAN_GROUP = ("f0", "f1", "w0", "w1", "slots", "set", "stream", "fuse_blend", "split_g", "finish", "fin_pass",
+              "p1_compact", "cam_shared", "cam_miss_once", "p1_lean", "row_compact", "row_cap", "blend", "n_steps")
+PLAN_STEP = ("finisher", "fgrid", "split", "split_out", "cam_n", "cam_shared", "n_trace", "trace0", "trace1",
+             "trace_grid", "classify", "classify_grid", "p1_count", "p1_grid0", "p1_grid1", "shade", "shade_grid")
+PLAN_TRACE = ("CAM_SMALL", "P1_SMALL", "REG_SMALL", "P1_SHADOW", "P1_CONT_LEAN", "P1_CONT", "SHADOW", "CONT",
+              "CAM_CW", "P1_CW", "REG_CW", "CAM_CB", "P1_CB", "REG_CB", "CAM_W", "P1_W", "REG_W", "CAM_B", "P1_B",
+              "REG_B")
+PLAN_SHADE = ("PLAIN", "BULK", "CAM", "FUSED", "CAM_LEAN", "BULK_LEAN")
+
+
+def render_plan_values(inputs: dict, max_values: int = 4096) -> list:
+    """rts_render_plan's output values (rt_scene.h) for `inputs`, a dict with every name of
+    PLAN_INPUTS."""
+    assert len(inputs) == len(PLAN_INPUTS), sorted(set(inputs) ^ set(PLAN_INPUTS))
+    vin = (C.c_int64 * len(PLAN_INPUTS))(*[int(inputs[k]) for k in PLAN_INPUTS])
+    out = (C.c_int64 * max_values)()
+    cnt = C.c_int32()
+    _check(lib().rts_render_plan(vin, len(PLAN_INPUTS), out, max_values, C.byref(cnt)), "rts_render_plan")
+    return out[:cnt.value]
+
+
+def render_plan(inputs: dict, max_values: int = 4096) -> dict:
+    """What one wavefront batch launches for `inputs` (render_plan_values, by name): the PLAN_HEAD
+    values and "groups", a list of dicts with the PLAN_GROUP values and "steps", a list of dicts of
+    PLAN_STEP values (all ints)."""
+    return decode_plan(render_plan_values(inputs, max_values))
+
+
+def decode_plan(v: list) -> dict:
+    plan = dict(zip(PLAN_HEAD, v), groups=[])
+    at = len(PLAN_HEAD)
+    for _ in range(plan["G"]):
+        g = dict(zip(PLAN_GROUP, v[at:at + len(PLAN_GROUP)]), steps=[])
+        at += len(PLAN_GROUP)
+        for _ in range(g["n_steps"]):
+            g["steps"].append(dict(zip(PLAN_STEP, v[at:at + len(PLAN_STEP)])))
+            at += len(PLAN_STEP)
+        plan["groups"].append(g)
+    assert at == len(v), (at, len(v))
+    return plan
 
 
 @dataclasses.dataclass
