@@ -61,7 +61,8 @@
  *    stays 7, and a binding finds it by symbol (a library built before it lacks rt_denoise).
  *    The temporal stage of the displayed frame (RT_HAS_TEMPORAL: rt_temporal_params, RT_TEMPORAL_*,
  *    rt_temporal_default_params, rt_temporal_async, rt_temporal, rt_temporal_history) is one more
- *    addition within ABI 7, found the same way.
+ *    addition within ABI 7, found the same way, and so is its motion mode (RT_HAS_TEMPORAL_MOTION:
+ *    rt_temporal_set_motion, rt_temporal_get_motion).
  * A binding checks rt_abi_version() at load time. */
 #define RT_ABI_VERSION 7
 #define RT_HAS_DENOISE 1
@@ -188,7 +189,7 @@ int rt_update_materials(rt_ctx* ctx, int32_t first, int32_t count, const rt_mate
  *   Like rt_update_materials, both calls wait for the render calls in flight, work on the context's
  * stream and return when the update is complete.  They leave LoopNum, the accumulation, rt_stats,
  * rt_order_work's order, the materials and the temporal history as they were (the caller resets what it
- * wants reset) and forget the current denoise / temporal guides: RT_DENOISE_REUSE_GUIDES and
+ * wants reset; with rt_temporal_set_motion the history follows the moved triangles) and forget the current denoise / temporal guides: RT_DENOISE_REUSE_GUIDES and
  * RT_TEMPORAL_REUSE_GUIDES return RT_ERR_STATE until a call packs fresh ones.  Every rank of a
  * multi-rank job makes the same call (each rank holds the whole scene).
  *   RT_ERR_STATE before rt_set_scene.  RT_ERR_ARG, with the scene untouched: count < 0, a null array with
@@ -202,8 +203,8 @@ int rt_update_materials(rt_ctx* ctx, int32_t first, int32_t count, const rt_mate
  * TRI / TRX / TRIN with at least one triangle's worth for TRX, 128 per triangle for HREC, 64 per binary
  * node, 128 per 4-wide node); rt_scene_bounds returns the scene's margins {cull_R, cull_K, cull_off,
  * tri_k1, tri_k0} and the number of triangles the edge filter leaves to the reference's test.  Both are
- * for tests and tooling.  Out of scope: topology changes, shrinking the margins, reprojecting a moving
- * surface's display history, an asynchronous update. */
+ * for tests and tooling.  Out of scope: topology changes, shrinking the margins, an asynchronous update
+ * (the display history of a moved surface: rt_temporal_set_motion). */
 #define RT_HAS_GEOMETRY_UPDATE 1
 int rt_update_geometry(rt_ctx* ctx, const int32_t* tri_index, int32_t first, int32_t count, const float* p1,
                        const float* p2, const float* p3, const float* n1, const float* n2, const float* n3);
@@ -480,9 +481,9 @@ int rt_denoise(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_params* 
  * (n H + k acc_k) / (n + k) against a frozen H.  Pass ADVANCE on the first display after the
  * accumulation restarted.  RT_TEMPORAL_RESET drops history and candidate before the call;
  * rt_resize and rt_set_scene drop them too.
- * Out of scope: reprojecting the history of a surface rt_update_geometry moved (the caller resets it:
- * RT_TEMPORAL_RESET), view-dependent (specular) reprojection, variance
- * estimation, multi-rank contexts (RT_ERR_STATE when world != 1). */
+ * A surface rt_update_geometry moved keeps its history only in the motion mode (below); without it
+ * the caller resets (RT_TEMPORAL_RESET).  Out of scope: view-dependent (specular) reprojection,
+ * variance estimation, multi-rank contexts (RT_ERR_STATE when world != 1). */
 #define RT_HAS_TEMPORAL 1
 typedef struct rt_temporal_params {
   int32_t samples;                  /* >= 1: samples per pixel in the input frame (LoopNum) */
@@ -518,6 +519,41 @@ int rt_temporal(rt_ctx* ctx, const rt_frame_params* fp, const rt_temporal_params
 /* The history lengths n_out of the last temporal call's output: width*height floats,
  * RT_LAYOUT_FRAME order; synchronous.  RT_ERR_STATE when there is none (no call yet, or dropped). */
 int rt_temporal_history(rt_ctx* ctx, float* n_out_host);
+
+/* ---- Motion mode of the temporal stage (RT_HAS_TEMPORAL_MOTION, an addition within ABI 7: find it
+ * by symbol).  Off (the default) the library does what is written above and nothing else: no
+ * allocation, launch or kernel argument differs.  On, every output of the stage remembers the pose
+ * of the scene it was made from (a copy of the vertex records RT_SCENE_TRI and RT_SCENE_TRIN, 96 B per
+ * triangle and history frame, copied device to device once per geometry generation and frame: a
+ * successful rt_update_geometry(_device) with count > 0 starts a generation), and a fresh pack of the
+ * guides (by rt_temporal_async or rt_denoise_async) also stores each pixel's first-hit triangle, 4 B per
+ * pixel and guide pair.  A hit pixel whose triangle T lies in [0, n_triangles) and has any of its 18
+ * floats (three positions, three vertex normals; bitwise) differing between the history's pose
+ * (q1..q3, m1..m3) and the current one (p1..p3, n1..n3) is reprojected through that triangle; every
+ * other pixel runs the arithmetic above bit for bit.  fp32, one correctly rounded operation per
+ * step, dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, vector lines per component:
+ *   e1 = p2 - p1; e2 = p3 - p1; v = P - p1
+ *   d11 = dot(e1,e1); d12 = dot(e1,e2); d22 = dot(e2,e2); v1 = dot(v,e1); v2 = dot(v,e2)
+ *   den = d11 d22 - d12 d12                                              require den > 0
+ *   b2 = (d22 v1 - d12 v2) / den; b3 = (d11 v2 - d12 v1) / den; b1 = (1 - b2) - b3   require all finite
+ *   Pq = q1 + (b2 (q2 - q1) + b3 (q3 - q1))
+ *   Nc = (b1 n1 + b2 n2) + b3 n3; flip = dot(N, Nc) < 0
+ *   Nm = (b1 m1 + b2 m2) + b3 m3; l = sqrt(dot(Nm,Nm))                   require l > 0 and finite
+ *   Nq = Nm / l, negated when flip
+ * and the stage runs with Pq in place of P in the projection and the tap tests, Nq in place of N:
+ * |Nq - N[q]|^2 <= sigma_normal^2, |dot(Nq, P[q] - Pq)| / t <= sigma_plane.  A failed `require`
+ * means no history for that pixel.  (The barycentrics are the 3D ones: the reference's xy-projected
+ * ones, RT:282-295, degenerate for a triangle edge-on to the xy plane.)  tests/temporal_motion_model.py
+ * is the same in numpy.  Triangle indices in a caller's hits_dev outside the list take the static path.
+ *   rt_temporal_set_motion waits for the work in flight (as rt_set_pipeline), drops history,
+ * candidate and poses (as RT_TEMPORAL_RESET) and frees or forgets the mode's buffers; any time after
+ * rt_create; RT_ERR_ARG unless on is 0 or 1.  The setting survives rt_set_scene and rt_resize, which
+ * drop the poses with the history.  RT_TEMPORAL_REUSE_GUIDES in motion mode reads the stored triangle
+ * frame and gives what fresh guides give; RT_ERR_STATE when the current guides were packed while the
+ * mode was off.  Out of scope: topology changes, motion vectors as an output. */
+#define RT_HAS_TEMPORAL_MOTION 1
+int rt_temporal_set_motion(rt_ctx* ctx, int32_t on);   /* 0 / 1; default 0 */
+int rt_temporal_get_motion(const rt_ctx* ctx, int32_t* on);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,38 @@ inline History history(size_t npx) {
   return L;
 }
 
+// The motion mode of the display history (rt_temporal_set_motion; rt_ctx::Motion), two allocations of
+// their own that exist only while the mode is on.  Poses: per {r, g, b, n} frame of History (col[k])
+// a copy of the scene's vertex records d_tri and d_trin, 3 float4 per triangle each (the scene's
+// size: dropped by rt_set_scene).  Triangle frames: per guide pair (0: the denoiser's, then History's
+// two) the int32 first-hit triangle of each pixel (the frame's size: dropped by rt_resize).
+constexpr size_t kTriRecBytes = 3 * 16;  // one triangle of d_tri, and of d_trin
+struct Poses {
+  Span tri[2], trin[2];
+  size_t total = 0;
+};
+inline Poses poses(size_t n_tri) {
+  Poses L;
+  Builder b;
+  for (int k = 0; k < 2; k++) {
+    L.tri[k] = b.add(n_tri * kTriRecBytes);
+    L.trin[k] = b.add(n_tri * kTriRecBytes);
+  }
+  L.total = b.total();
+  return L;
+}
+struct TriFrames {
+  Span tf[3];
+  size_t total = 0;
+};
+inline TriFrames tri_frames(size_t npx) {
+  TriFrames L;
+  Builder b;
+  for (Span& f : L.tf) f = b.add(npx * 4);
+  L.total = b.total();
+  return L;
+}
+
 // ---- frame table (rt_ctx::FrameTable), in ints ---------------------------------------------------
 // [cap] loop_num, [cap] rand_origin, then what wf_sobol adds: [cap][4] float2 Sobol pairs and [cap]
 // float2 blend weights.  The pinned host copy holds the two uploaded sub-tables alone.

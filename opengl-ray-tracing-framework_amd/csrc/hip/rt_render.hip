@@ -261,8 +261,26 @@ struct rt_ctx {
     int hist = -1, cand = -1;             // index into col; -1: none
     int hist_g = -1, cand_g = -1;         // their guide pairs
     rt_frame_params hist_fp{}, cand_fp{}; // the cameras they were seen from
-    void drop() { hist = cand = hist_g = cand_g = -1; }
+    long long pose_gen[2] = {-1, -1};     // motion mode: the geometry generation Motion's pose slot of col[k] holds; -1: none
+    void drop() {
+      hist = cand = hist_g = cand_g = -1;
+      pose_gen[0] = pose_gen[1] = -1;
+    }
   } tp;
+  // The motion mode of the display history (rt_temporal_set_motion; dvl::Poses, dvl::TriFrames):
+  // nothing of it exists while the mode is off.  Pose slot k goes with tp.col[k] (it follows its frame
+  // through ADVANCE with the index) and is filled, once per generation and slot, by the temporal call
+  // that writes that frame; triangle frame k goes with guide pair k and is written by a fresh pack.
+  struct Motion {
+    bool on = false;                      // survives rt_set_scene and rt_resize
+    long long gen = 0;                    // the geometry generation: rt_update_geometry(_device) with count > 0
+    void* pose_mem = nullptr;             // for n_tri triangles: freed by rt_set_scene
+    float4* tri[2] = {nullptr, nullptr};
+    float4* trin[2] = {nullptr, nullptr};
+    void* tf_mem = nullptr;               // for W*H pixels: freed by a resize
+    int* tf[3] = {nullptr, nullptr, nullptr};
+    bool tf_valid[3] = {false, false, false};  // the pair's guides were packed with its triangle frame
+  } mo;
 };
 
 namespace {
@@ -685,6 +703,21 @@ void geo_drop(rt_ctx* c) {
   g.planned = false;
 }
 
+// The motion mode's two allocations (rt_ctx::Motion): the poses of the display history's frames, and
+// the triangle frames of the guide pairs.  The callers have drained the context.
+void motion_free_poses(rt_ctx* c) {
+  rt_ctx::Motion& m = c->mo;
+  if (m.pose_mem) (void)hipFree(m.pose_mem);
+  m.pose_mem = nullptr;
+  c->tp.pose_gen[0] = c->tp.pose_gen[1] = -1;
+}
+void motion_free_frames(rt_ctx* c) {
+  rt_ctx::Motion& m = c->mo;
+  if (m.tf_mem) (void)hipFree(m.tf_mem);
+  m.tf_mem = nullptr;
+  for (bool& v : m.tf_valid) v = false;
+}
+
 // ---- rt_update_geometry (rt_geometry.h; the definition is scn::update_geometry)
 // The refit schedule and the reduction cell, on the first update after a rt_set_scene: the node
 // arrays come from the device, so a context that never updates geometry keeps no copy of them
@@ -799,6 +832,8 @@ int rt_destroy(rt_ctx* c) {
   dfree(c->q.d_ovf);
   if (c->dn.mem) (void)hipFree(c->dn.mem);
   if (c->tp.mem) (void)hipFree(c->tp.mem);
+  motion_free_poses(c);
+  motion_free_frames(c);
   dfree(c->d_disp);
   dfree(c->d_gather);
   for (auto& m : c->rccl_comms) (void)ncclCommDestroy(m);
@@ -830,6 +865,8 @@ int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   // without one (renders and queries then refuse) rather than with a mix of old and new buffers
   c->scene_set = false;
   c->tp.drop();  // the display history shows another scene
+  motion_free_poses(c);  // (its poses are another triangle list's)
+  c->mo.gen = 0;
   geo_drop(c);   // and the refit schedule is another tree's
   int rc;
   if ((rc = upload(c, (void**)&c->d_qnodes, k.qnodes.data(), k.qnodes.size() * sizeof(scn::WNode)))) return rc;
@@ -945,6 +982,7 @@ int rt_update_geometry_device(rt_ctx* c, const void* tri_index_dev, int32_t firs
                      c->d_tri, c->d_trx, c->d_trin, c->d_hrec, g.d_red);
   HIPCHK(c, hipGetLastError());
   c->dn.guides = false;  // the denoise / temporal guides show the old surfaces (the history stays: the caller resets)
+  c->mo.gen++;           // a new pose: in motion mode the history follows the moved triangles from its own
   if (g.n_leaves > 0) {
     hipLaunchKernelGGL(rtg::geo_leaf, dim3((g.n_leaves + 255) / 256), block, 0, c->stream, g.d_leaves, g.n_leaves, c->d_tri,
                        reinterpret_cast<scn::BNode*>(c->d_nodes), reinterpret_cast<scn::WNode*>(c->d_qnodes));
@@ -1068,6 +1106,7 @@ static int apply_tiling(rt_ctx* c, int width, int height, const rt_tiling& tl, s
   c->dn = rt_ctx::Denoise{};
   if (c->tp.mem) (void)hipFree(c->tp.mem);  // and so is the display history
   c->tp = rt_ctx::Temporal{};
+  motion_free_frames(c);  // and its triangle frames
   c->W = width; c->H = height;
   c->tile_w = tl.tile_w; c->tile_h = tl.tile_h; c->rank = tl.rank; c->world = tl.world;
   c->tiles_x = (width + tl.tile_w - 1) / tl.tile_w;
@@ -2612,6 +2651,30 @@ int reserve_temporal(rt_ctx* c) {
   return RT_OK;
 }
 
+// The motion mode's buffers (the mode is on): the triangle frames for the current frame size, the
+// pose slots for the current scene
+int reserve_tri_frames(rt_ctx* c) {
+  rt_ctx::Motion& m = c->mo;
+  if (m.tf_mem) return RT_OK;
+  const dvl::TriFrames L = dvl::tri_frames((size_t)c->W * c->H);
+  if (int rc = alloc_block(c, m.tf_mem, L.total, "triangle frames do not fit in device memory")) return rc;
+  for (int k = 0; k < 3; k++) place(m.tf[k], m.tf_mem, L.tf[k]);
+  for (bool& v : m.tf_valid) v = false;
+  return RT_OK;
+}
+int reserve_poses(rt_ctx* c) {
+  rt_ctx::Motion& m = c->mo;
+  if (m.pose_mem) return RT_OK;
+  const dvl::Poses L = dvl::poses((size_t)c->n_tri);
+  if (int rc = alloc_block(c, m.pose_mem, std::max<size_t>(L.total, 256), "scene poses do not fit in device memory")) return rc;
+  for (int k = 0; k < 2; k++) {
+    place(m.tri[k], m.pose_mem, L.tri[k]);
+    place(m.trin[k], m.pose_mem, L.trin[k]);
+  }
+  c->tp.pose_gen[0] = c->tp.pose_gen[1] = -1;
+  return RT_OK;
+}
+
 // The guide pair dn.g0 / dn.g1 point at (0, the denoiser's own, without a display history)
 int tp_current_pair(const rt_ctx* c) {
   for (int k = 1; k < 3; k++)
@@ -2654,6 +2717,8 @@ int display_pack(rt_ctx* c, const rt_frame_params* fp, bool reuse, const float* 
                  bool keep_cand, int& pair) {
   rt_ctx::Denoise& d = c->dn;
   pair = reuse ? tp_current_pair(c) : tp_guides_target(c, keep_cand);
+  if (!reuse && c->mo.on)
+    if (int rc = reserve_tri_frames(c)) return rc;
   if (!reuse && !hits_dev) {
     d.guides = false;  // (they are being replaced: a failure below leaves none)
     if (int rc = first_hit_launch(c, fp, d.hits)) return rc;
@@ -2668,6 +2733,14 @@ int display_pack(rt_ctx* c, const rt_frame_params* fp, bool reuse, const float* 
                        hits_dev ? (const float4*)hits_dev : d.hits, d.col[0], d.g0, d.g1, c->W, c->H, c->tile_w,
                        c->tile_h, c->tiles_x);
   HIPCHK(c, hipGetLastError());
+  if (!reuse) {  // the pair's triangle frame: this pack's in motion mode, else none
+    c->mo.tf_valid[pair] = c->mo.on;
+    if (c->mo.on) {
+      hipLaunchKernelGGL(rtd::tp_pack_tri, pgrid, dim3(256), 0, c->stream, hits_dev ? (const float4*)hits_dev : d.hits,
+                         c->mo.tf[pair], c->W, c->H, c->tile_w, c->tile_h, c->tiles_x);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
   d.guides = true;
   return RT_OK;
 }
@@ -2774,11 +2847,15 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
   if (tp->flags & ~(RT_TEMPORAL_ADVANCE | RT_TEMPORAL_REUSE_GUIDES | RT_TEMPORAL_RESET)) return fail(c, RT_ERR_ARG, "unknown flags");
   const bool reuse = (tp->flags & RT_TEMPORAL_REUSE_GUIDES) != 0;
   if (int rc = display_state(c, fp, reuse, true, "no guides of an earlier denoise or temporal call for this size")) return rc;
+  if (reuse && c->mo.on && !c->mo.tf_valid[tp_current_pair(c)])
+    return fail(c, RT_ERR_STATE, "the current guides were packed without their triangle frame (before rt_temporal_set_motion)");
   for (int a = 0; a < 3; a++)
     if (!std::isfinite(fp->front[a])) return fail(c, RT_ERR_ARG, "non-finite camera");
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = reserve_denoise(c)) return rc;
   if (int rc = reserve_temporal(c)) return rc;
+  if (c->mo.on)
+    if (int rc = reserve_poses(c)) return rc;
   rt_ctx::Denoise& d = c->dn;
   rt_ctx::Temporal& t = c->tp;
   // The previous output changes roles: the history (ADVANCE), or nothing (this call's replaces it)
@@ -2814,8 +2891,31 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
   T.sn2 = tp->sigma_normal * tp->sigma_normal;
   T.sp = tp->sigma_plane;
   const dim3 grid((unsigned)((c->W + rtd::kDnTW - 1) / rtd::kDnTW), (unsigned)((c->H + rtd::kDnTH - 1) / rtd::kDnTH));
-  hipLaunchKernelGGL(rtd::tp_resolve, grid, dim3(256), 0, c->stream, T);
+  rt_ctx::Motion& m = c->mo;
+  // The motion form only where the history was made from another pose than the current one
+  if (m.on && t.hist >= 0 && t.pose_gen[t.hist] >= 0 && t.pose_gen[t.hist] != m.gen) {
+    rtd::TpMotion Mo;
+    Mo.tf = m.tf[pair];
+    Mo.tri = c->d_tri;
+    Mo.trin = c->d_trin;
+    Mo.htri = m.tri[t.hist];
+    Mo.htrin = m.trin[t.hist];
+    Mo.n_tri = c->n_tri;
+    hipLaunchKernelGGL(rtd::tp_resolve_motion, grid, dim3(256), 0, c->stream, T, Mo);
+  } else {
+    hipLaunchKernelGGL(rtd::tp_resolve, grid, dim3(256), 0, c->stream, T);
+  }
   HIPCHK(c, hipGetLastError());
+  // The candidate was made from the current pose: its slot holds it, copied once per generation
+  if (m.on && t.pose_gen[cand] != m.gen) {
+    const size_t bytes = (size_t)c->n_tri * dvl::kTriRecBytes;
+    t.pose_gen[cand] = -1;
+    if (bytes) {
+      HIPCHK(c, hipMemcpyAsync(m.tri[cand], c->d_tri, bytes, hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(m.trin[cand], c->d_trin, bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    t.pose_gen[cand] = m.gen;
+  }
   t.cand = cand;
   t.cand_g = pair;
   t.cand_fp = *fp;
@@ -2829,6 +2929,23 @@ int rt_temporal(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_params* 
   float* out = nullptr;
   if (int rc = rt_temporal_async(c, fp, tp, nullptr, nullptr, &out)) return rc;
   return display_fetch(c, out, rgb_out_host);
+}
+
+int rt_temporal_set_motion(rt_ctx* c, int32_t on) {
+  if (!c) return RT_ERR_ARG;
+  if (on != 0 && on != 1) return fail(c, RT_ERR_ARG, "on is 0 or 1");
+  if (int rc = rt_synchronize(c)) return rc;  // (a temporal call in flight reads the buffers freed below)
+  c->tp.drop();
+  motion_free_poses(c);
+  motion_free_frames(c);
+  c->mo.on = on != 0;
+  return RT_OK;
+}
+
+int rt_temporal_get_motion(const rt_ctx* c, int32_t* on) {
+  if (!c || !on) return RT_ERR_ARG;
+  *on = c->mo.on ? 1 : 0;
+  return RT_OK;
 }
 
 int rt_temporal_history(rt_ctx* c, float* n_out_host) {

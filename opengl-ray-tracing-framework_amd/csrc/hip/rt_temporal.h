@@ -46,7 +46,71 @@ struct TpCall {
 
 RTD float tp_dot(const float* a, float x, float y, float z) { return (a[0] * x + a[1] * y) + a[2] * z; }
 
-__global__ __launch_bounds__(256) void tp_resolve(const TpCall T) {
+// What the motion form reads beside TpCall (rt_temporal_set_motion): the current
+// pixels' triangle indices and the vertex records {p_k, .}, {n_k, .} (3 float4 per triangle each) of
+// the current pose and of the pose the history was made from
+struct TpMotion {
+  const int* __restrict__ tf;         // the current guides' triangle frame: T, or -1 for a miss
+  const float4* __restrict__ tri;     // the current pose
+  const float4* __restrict__ trin;
+  const float4* __restrict__ htri;    // the history's pose
+  const float4* __restrict__ htrin;
+  int n_tri;
+};
+
+struct TpV3 {
+  float x, y, z;
+};
+RTD TpV3 tp_v3(const float4 a) { return TpV3{a.x, a.y, a.z}; }
+RTD TpV3 tp_sub(const TpV3 a, const TpV3 b) { return TpV3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+RTD float tp_dot3(const TpV3 a, const TpV3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+RTD TpV3 tp_bary(float b1, const TpV3 a, float b2, const TpV3 b, float b3, const TpV3 c) {
+  return TpV3{(b1 * a.x + b2 * b.x) + b3 * c.x, (b1 * a.y + b2 * b.y) + b3 * c.y, (b1 * a.z + b2 * b.z) + b3 * c.z};
+}
+RTD int tp_diff(const float4 a, const float4 b) {  // xyz, bitwise
+  return (__float_as_int(a.x) ^ __float_as_int(b.x)) | (__float_as_int(a.y) ^ __float_as_int(b.y)) |
+         (__float_as_int(a.z) ^ __float_as_int(b.z));
+}
+
+// The surface point P of triangle t (first-hit normal N) as the history's pose had it: false when t is
+// no triangle of the list or none of its 18 floats moved (P, N stay: today's arithmetic).  Otherwise
+// P, N become the point with P's barycentrics and its interpolated unit normal in the history's pose,
+// N on the side of the surface the hit normal is on; ok = false when a `require` fails (no history).
+RTD bool tp_moved(const TpMotion& m, int t, TpV3& P, TpV3& N, bool& ok) {
+  if ((unsigned)t >= (unsigned)m.n_tri) return false;
+  const size_t at = 3 * (size_t)t;
+  const float4 cp1 = m.tri[at], cp2 = m.tri[at + 1], cp3 = m.tri[at + 2];
+  const float4 cn1 = m.trin[at], cn2 = m.trin[at + 1], cn3 = m.trin[at + 2];
+  const float4 hp1 = m.htri[at], hp2 = m.htri[at + 1], hp3 = m.htri[at + 2];
+  const float4 hn1 = m.htrin[at], hn2 = m.htrin[at + 1], hn3 = m.htrin[at + 2];
+  if (!(tp_diff(cp1, hp1) | tp_diff(cp2, hp2) | tp_diff(cp3, hp3) | tp_diff(cn1, hn1) | tp_diff(cn2, hn2) | tp_diff(cn3, hn3)))
+    return false;
+  ok = false;
+  const TpV3 p1 = tp_v3(cp1), q1 = tp_v3(hp1);
+  const TpV3 e1 = tp_sub(tp_v3(cp2), p1), e2 = tp_sub(tp_v3(cp3), p1), v = tp_sub(P, p1);
+  const float d11 = tp_dot3(e1, e1), d12 = tp_dot3(e1, e2), d22 = tp_dot3(e2, e2), v1 = tp_dot3(v, e1), v2 = tp_dot3(v, e2);
+  const float den = d11 * d22 - d12 * d12;
+  if (!(den > 0.0f)) return true;
+  const float b2 = (d22 * v1 - d12 * v2) / den, b3 = (d11 * v2 - d12 * v1) / den, b1 = (1.0f - b2) - b3;
+  if (!(isfinite(b1) && isfinite(b2) && isfinite(b3))) return true;
+  const TpV3 f1 = tp_sub(tp_v3(hp2), q1), f2 = tp_sub(tp_v3(hp3), q1);
+  const TpV3 Pq{q1.x + (b2 * f1.x + b3 * f2.x), q1.y + (b2 * f1.y + b3 * f2.y), q1.z + (b2 * f1.z + b3 * f2.z)};
+  const TpV3 Nc = tp_bary(b1, tp_v3(cn1), b2, tp_v3(cn2), b3, tp_v3(cn3));
+  const bool flip = tp_dot3(N, Nc) < 0.0f;
+  const TpV3 Nm = tp_bary(b1, tp_v3(hn1), b2, tp_v3(hn2), b3, tp_v3(hn3));
+  const float l = sqrtf(tp_dot3(Nm, Nm));
+  if (!(l > 0.0f && isfinite(l))) return true;
+  const TpV3 Nq{Nm.x / l, Nm.y / l, Nm.z / l};
+  P = Pq;
+  N = flip ? TpV3{-Nq.x, -Nq.y, -Nq.z} : Nq;
+  ok = true;
+  return true;
+}
+
+// MOTION = false is tp_resolve as it always was; with MOTION a pixel of a moved triangle enters the
+// same statements with the history pose's P and N in place of its own.
+template <bool MOTION>
+RTD void tp_resolve_px(const TpCall& T, const TpMotion* mo) {
   const int px = (int)blockIdx.x * kDnTW + ((int)threadIdx.x & 31), py = (int)blockIdx.y * kDnTH + ((int)threadIdx.x >> 5);
   if (px >= T.W || py >= T.H) return;
   const size_t pi = (size_t)py * (size_t)T.W + (size_t)px;
@@ -58,9 +122,12 @@ __global__ __launch_bounds__(256) void tp_resolve(const TpCall T) {
     float sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f, sw = 0.0f;
     if (T.hc) {
       const float4 p = T.g1[pi];
-      const float dx = p.x - T.pos[0], dy = p.y - T.pos[1], dz = p.z - T.pos[2];
+      TpV3 P{p.x, p.y, p.z}, N{a.x, a.y, a.z};
+      bool ok = true;
+      if (MOTION) tp_moved(*mo, mo->tf[pi], P, N, ok);
+      const float dx = P.x - T.pos[0], dy = P.y - T.pos[1], dz = P.z - T.pos[2];
       const float df = tp_dot(T.front, dx, dy, dz);
-      if (df > 0.0f) {
+      if (ok && df > 0.0f) {
         const float k = tp_dot(T.front, T.lbc[0], T.lbc[1], T.lbc[2]) / df;
         const float ca = k * tp_dot(T.right, dx, dy, dz) - tp_dot(T.right, T.lbc[0], T.lbc[1], T.lbc[2]);
         const float cb = k * tp_dot(T.up, dx, dy, dz) - tp_dot(T.up, T.lbc[0], T.lbc[1], T.lbc[2]);
@@ -83,10 +150,10 @@ __global__ __launch_bounds__(256) void tp_resolve(const TpCall T) {
               const size_t qi = (size_t)qy * (size_t)T.W + (size_t)qx;
               const float4 cq = T.hc[qi], aq = T.hg0[qi], bq = T.hg1[qi];
               const float w = (i ? wx1 : wx0) * (j ? wy1 : wy0);
-              const float nx = a.x - aq.x, ny = a.y - aq.y, nz = a.z - aq.z;
+              const float nx = N.x - aq.x, ny = N.y - aq.y, nz = N.z - aq.z;
               const float dn2 = (nx * nx + ny * ny) + nz * nz;
-              const float qx_ = bq.x - p.x, qy_ = bq.y - p.y, qz_ = bq.z - p.z;
-              const float d = ((a.x * qx_ + a.y * qy_) + a.z * qz_);
+              const float qx_ = bq.x - P.x, qy_ = bq.y - P.y, qz_ = bq.z - P.z;
+              const float d = ((N.x * qx_ + N.y * qy_) + N.z * qz_);
               if (cq.w > 0.0f && dn_finite(cq) && __float_as_int(aq.w) == M && dn2 <= T.sn2 && fabsf(d) * p.w <= T.sp) {
                 sr = sr + cq.x * w;
                 sg = sg + cq.y * w;
@@ -117,6 +184,21 @@ __global__ __launch_bounds__(256) void tp_resolve(const TpCall T) {
   T.cand[pi] = make_float4(r, g, b, n);
   float* o = T.out3 + 3 * pi;
   o[0] = r; o[1] = g; o[2] = b;
+}
+
+__global__ __launch_bounds__(256) void tp_resolve(const TpCall T) { tp_resolve_px<false>(T, nullptr); }
+__global__ __launch_bounds__(256) void tp_resolve_motion(const TpCall T, const TpMotion Mo) { tp_resolve_px<true>(T, &Mo); }
+
+// The triangle frame of a fresh pack on a context in motion mode (the guide texels do not hold the
+// triangle index): T of the rt_hit records in local-tile order, or -1 for a miss, in frame order
+__global__ __launch_bounds__(256) void tp_pack_tri(const float4* __restrict__ hits, int* __restrict__ tf, int W, int H,
+                                                   int tile_w, int tile_h, int tiles_x) {
+  const int px = (int)(blockIdx.x * blockDim.x + threadIdx.x), py = (int)blockIdx.y;
+  if (px >= W || py >= H) return;
+  const int tx = px / tile_w, ty = py / tile_h;
+  const size_t ti = (size_t)(ty * tiles_x + tx) * (size_t)(tile_w * tile_h) + (size_t)(py - ty * tile_h) * tile_w + (px - tx * tile_w);
+  const int t = __float_as_int(hits[3 * ti + 2].x);
+  tf[(size_t)py * (size_t)W + (size_t)px] = t >= 0 ? t : -1;
 }
 
 }  // namespace rtd

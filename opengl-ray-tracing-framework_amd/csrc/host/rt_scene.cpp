@@ -1369,6 +1369,18 @@ int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_
       for (size_t p = 0; p < m; p++) put(L.org(p), 0, -1, true);
       break;
     }
+    case RTS_LAYOUT_POSES: {
+      const dvl::Poses L = dvl::poses(n);
+      scalars[0] = L.total;
+      for (dvl::Span at : {L.tri[0], L.trin[0], L.tri[1], L.trin[1]}) put(at, 0, -1, true);
+      break;
+    }
+    case RTS_LAYOUT_TRI_FRAMES: {
+      const dvl::TriFrames L = dvl::tri_frames(n);
+      scalars[0] = L.total;
+      for (dvl::Span at : L.tf) put(at, 0, -1, true);
+      break;
+    }
     default: return RTS_ERR_ARG;
   }
   *n_spans = k;

@@ -117,6 +117,7 @@ class Settings:
     max_iterations: int = 3000
     enable_denoise: bool = False  # (no counterpart in the reference) rt_denoise before the display pass
     enable_temporal: bool = False  # (likewise) rt_temporal before both: the display history follows the camera
+    enable_temporal_motion: bool = False  # rt_temporal_set_motion: and the triangles Input.geometry moved
 
 
 # OnGUI controls that restart the accumulation (main.cpp:343-368, :408); tone mapping / gamma
@@ -178,6 +179,7 @@ class Session:
         # the next temporal call is the first display since the accumulation restarted (or since the
         # stage was last on): the previous call's output becomes the history (RT_TEMPORAL_ADVANCE)
         self._advance = True
+        self._motion = False  # the context's motion mode as this session last set it (Settings.enable_temporal_motion)
 
     # main.cpp:296-318
     def _mouse(self, xpos: float, ypos: float, rmb: bool) -> None:
@@ -223,6 +225,11 @@ class Session:
                 raise KeyError(f"unknown setting {name!r}")
             setattr(self.settings, name, value)
             reset |= name in RESETTING
+        if bool(self.settings.enable_temporal_motion) != self._motion:  # (drops the display history, like a resize)
+            self._motion = bool(self.settings.enable_temporal_motion)
+            self.r.set_temporal_motion(self._motion)
+            self._guides_current = False
+            self._advance = True
         if inp.camera_position is not None:
             self.camera.position = np.array(inp.camera_position, f32)
             self.camera.refresh()

@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "rt_get_triangle_material",
     "rt_denoise_default_params", "rt_denoise_async", "rt_denoise",
     "rt_temporal_default_params", "rt_temporal_async", "rt_temporal", "rt_temporal_history",
+    "rt_temporal_set_motion", "rt_temporal_get_motion",
     "rt_update_geometry", "rt_update_geometry_device", "rt_scene_download", "rt_scene_array_bytes",
     "rt_scene_bounds",
 )
@@ -57,6 +58,7 @@ RT_DISPLAY_TONEMAP, RT_DISPLAY_GAMMA = 1, 2
 RT_HAS_DENOISE = 1
 RT_DENOISE_REUSE_GUIDES = 1
 RT_HAS_TEMPORAL = 1
+RT_HAS_TEMPORAL_MOTION = 1
 RT_HAS_GEOMETRY_UPDATE = 1
 # rt_scene_download's arrays and the dtype / row shape each comes back as
 SCENE_ARRAYS = ("tri", "trx", "trin", "hrec", "nodes", "qnodes")
@@ -333,6 +335,9 @@ def _bind(L: C.CDLL) -> C.CDLL:
         L.rt_temporal_async.argtypes = [vp, fpp, tpp, vp, vp, C.POINTER(vp)]
         L.rt_temporal.argtypes = [vp, fpp, tpp, _f32p]
         L.rt_temporal_history.argtypes = [vp, _f32p]
+    if hasattr(L, "rt_temporal_set_motion"):  # RT_HAS_TEMPORAL_MOTION (likewise)
+        L.rt_temporal_set_motion.argtypes = [vp, C.c_int32]
+        L.rt_temporal_get_motion.argtypes = [vp, _i32p]
     if hasattr(L, "rt_update_geometry"):  # RT_HAS_GEOMETRY_UPDATE (likewise)
         L.rt_update_geometry.argtypes = [vp, _i32p, C.c_int32, C.c_int32] + [_f32p] * 6
         L.rt_update_geometry_device.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 6
@@ -687,6 +692,16 @@ class Renderer:
         self._check(self._L.rt_temporal_async(self._h, C.byref(p), C.byref(t), C.c_void_p(frame_ptr) if frame_ptr else None,
                                               C.c_void_p(hits_ptr) if hits_ptr else None, C.byref(out)), "rt_temporal_async")
         return out.value or 0
+
+    def set_temporal_motion(self, on: bool) -> None:
+        """rt_temporal_set_motion: the temporal stage follows triangles that update_geometry moved
+        (waits for the work in flight; drops the display history)."""
+        self._check(self._L.rt_temporal_set_motion(self._h, 1 if on else 0), "rt_temporal_set_motion")
+
+    def get_temporal_motion(self) -> bool:
+        on = C.c_int32()
+        self._check(self._L.rt_temporal_get_motion(self._h, C.byref(on)), "rt_temporal_get_motion")
+        return bool(on.value)
 
     def temporal_history(self) -> np.ndarray:
         """rt_temporal_history: (H, W) float32 history lengths of the last temporal call's output."""
