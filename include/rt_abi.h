@@ -62,7 +62,9 @@
  *    The temporal stage of the displayed frame (RT_HAS_TEMPORAL: rt_temporal_params, RT_TEMPORAL_*,
  *    rt_temporal_default_params, rt_temporal_async, rt_temporal, rt_temporal_history) is one more
  *    addition within ABI 7, found the same way, and so is its motion mode (RT_HAS_TEMPORAL_MOTION:
- *    rt_temporal_set_motion, rt_temporal_get_motion).
+ *    rt_temporal_set_motion, rt_temporal_get_motion) and the variance mode of the two stages
+ *    (RT_HAS_VARIANCE: rt_variance_params, rt_variance_default_params, rt_variance_set,
+ *    rt_variance_get, rt_variance_frame).
  * A binding checks rt_abi_version() at load time. */
 #define RT_ABI_VERSION 7
 #define RT_HAS_DENOISE 1
@@ -416,7 +418,8 @@ int rt_get_triangle_material(rt_ctx* ctx, int32_t triangle, rt_material* out, in
  * bit (they show the environment, which carries no noise); a non-finite pixel is never a source and
  * is filled from its neighbours by the geometric weights alone.
  * Out of scope: multi-rank contexts (a rank has guides for its own pixels only: RT_ERR_STATE when
- * world != 1), variance estimation, albedo demodulation (temporal reprojection: rt_temporal*, below). */
+ * world != 1), albedo demodulation (temporal reprojection: rt_temporal*, variance guidance:
+ * rt_variance_*, both below). */
 typedef struct rt_denoise_params {
   int32_t iterations;               /* 1..5 */
   float sigma_color, sigma_normal, sigma_plane;   /* each finite and > 0 */
@@ -483,7 +486,7 @@ int rt_denoise(rt_ctx* ctx, const rt_frame_params* fp, const rt_denoise_params* 
  * rt_resize and rt_set_scene drop them too.
  * A surface rt_update_geometry moved keeps its history only in the motion mode (below); without it
  * the caller resets (RT_TEMPORAL_RESET).  Out of scope: view-dependent (specular) reprojection,
- * variance estimation, multi-rank contexts (RT_ERR_STATE when world != 1). */
+ * multi-rank contexts (RT_ERR_STATE when world != 1); variance estimation: rt_variance_*, below. */
 #define RT_HAS_TEMPORAL 1
 typedef struct rt_temporal_params {
   int32_t samples;                  /* >= 1: samples per pixel in the input frame (LoopNum) */
@@ -554,6 +557,66 @@ int rt_temporal_history(rt_ctx* ctx, float* n_out_host);
 #define RT_HAS_TEMPORAL_MOTION 1
 int rt_temporal_set_motion(rt_ctx* ctx, int32_t on);   /* 0 / 1; default 0 */
 int rt_temporal_get_motion(const rt_ctx* ctx, int32_t* on);
+
+/* ---- Variance mode of the display chain (RT_HAS_VARIANCE, an addition within ABI 7: find it by
+ * symbol).  Off (the default) the temporal stage and the denoiser do what is written above and
+ * nothing else: no allocation, launch, kernel argument or output bit differs.  On, the temporal
+ * stage estimates the per-sample variance of every pixel's luminance l = (0.2126 r + 0.7152 g) +
+ * 0.0722 b from the inputs it sees, and the denoiser replaces its fixed colour term by a luminance
+ * term scaled by the variance of what it filters (Schied et al. 2017, SVGF), so that a converged
+ * view is no longer blurred.  fp32, one correctly rounded operation per step, in the order written;
+ * tests/variance_model.py is the same in numpy and the kernels agree with it bit for bit.
+ *   Temporal stage.  Beside each {r, g, b, n} texel of history and candidate lies one state texel
+ * {l_prev, S_prev, v, m} (16 B): luminance and sample count of the last input seen for the view, the
+ * running mean v of m variance estimates.  Per hit pixel with input luminance l_c, S = samples:
+ *   a call without RT_TEMPORAL_ADVANCE / RESET after an earlier call (the same view, accumulated
+ *   further) reads its own texel of the candidate before overwriting it; with a finite input and
+ *   S > S_prev > 0:  dS = S - S_prev; s = (S l_c - S_prev l_prev) / dS; d = s - l_prev;
+ *                    e = (d d) ((dS S_prev) / S)            (Welford's chunk-merge term)
+ *   any other call takes v0 = sum(w vq) / sw, m0 = sum(w mq) / sw over the colour's counting taps
+ *   (0, 0 without history); with history and a finite input, l_h the luminance of the history h:
+ *                    d = l_c - l_h; e = (d d) / (1 / S + 1 / n_h)
+ *   Either e is one squared difference of two independent means, unbiased for the per-sample
+ *   variance.  With a finite e:  v = v0 + (e - v0) / (m0 + 1); m = min(m0 + 1, max_estimates); else
+ *   v, m = v0, m0.  A finite input stores l_prev = l_c, S_prev = S; a non-finite one keeps both
+ *   (0, 0 in the second case); a miss stores zeros.  The variance of the displayed luminance:
+ *   var = v / max(n_out, S) when m > 0, else -1 (unknown).
+ *   Denoiser.  The input's variance is the temporal stage's when frame_in_device is the pointer the
+ * last rt_temporal_async returned, else unknown everywhere.  A hit pixel with var < 0 takes the
+ * spatial estimate: over the 7 x 7 neighbours q (dy outer, dx inner, the centre included) with the
+ * centre's material, a finite colour, |N - Nq|^2 <= sigma_normal^2 and |N . (Pq - P)| / t <=
+ * sigma_plane, with d = l_q - (l_p, or 0 when p is not finite): s1 = sum d, s2 = sum d d, and
+ * var = max((s2 - (s1 s1) / cnt) / (cnt - 1), 0) when cnt >= 2; a pixel that stays unknown keeps the
+ * fixed sigma_color term.  Iteration i, for a pixel with var_p >= 0: g = sum(w3 var_q) / sum(w3) over
+ * the 3 x 3 neighbours with p's material and var_q >= 0, w3 = {1/4, 1/2, 1/4}^2; kl = 1 / (sigma_lum
+ * sqrt(g) + 1e-8); the colour term of a tap's exponent becomes |l_p - l_q| kl (0 for a non-finite p),
+ * geometric terms, B3 weights, tap order and tap tests unchanged.  The iteration's output carries
+ * var' = sum(w^2 var_q over counting taps with var_q >= 0) / (sum w)^2 where var_p >= 0 and a tap
+ * counted, else var_p.  Miss pass-through, non-finite filling and the bit-identical return of
+ * per-material constant frames hold as without the mode.
+ *   rt_variance_set waits for the work in flight, drops history and candidate (as
+ * RT_TEMPORAL_RESET) and, when on == 0, frees the mode's buffers (44 B per pixel: two state frames,
+ * three variance frames; allocated by the first temporal or denoise call in the mode, re-sized by
+ * rt_resize).  The setting survives rt_set_scene and rt_resize.  It composes with the motion mode: v
+ * and m ride the colour's taps, moved triangles included.  RT_ERR_ARG: a null pointer, on outside
+ * 0 / 1, sigma_lum not finite and > 0, max_estimates < 1, flags != 0.
+ * Out of scope: a second-moment accumulation inside the renderer, specular reprojection, multi-rank
+ * contexts. */
+#define RT_HAS_VARIANCE 1
+typedef struct rt_variance_params {
+  int32_t on;                       /* 0 / 1; default 0 */
+  float sigma_lum;                  /* finite and > 0: luminance differences in standard deviations */
+  int32_t max_estimates;            /* >= 1: cap of m (from there on v is an exponential average) */
+  int32_t flags;                    /* 0 */
+} rt_variance_params;               /* 16 bytes */
+/* The defaults: on 0, sigma_lum 1.5, max_estimates 64, flags 0. */
+int rt_variance_default_params(rt_variance_params* vp);
+int rt_variance_set(rt_ctx* ctx, const rt_variance_params* vp);
+int rt_variance_get(const rt_ctx* ctx, rt_variance_params* vp);
+/* The variance of the displayed luminance of the last temporal or denoise call's output in the mode:
+ * width*height floats, RT_LAYOUT_FRAME order, -1 where it is unknown; synchronous.  RT_ERR_STATE when
+ * there is none (mode off, no call yet, or dropped by rt_resize / rt_variance_set). */
+int rt_variance_frame(rt_ctx* ctx, float* var_out_host);
 
 #ifdef __cplusplus
 }

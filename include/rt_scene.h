@@ -144,9 +144,10 @@ int rts_tri_filter(const float* tri, int n_triangles, float* out, double* k, int
  *   CAMERA_TABLE n work items, m <= 8 pipeline sets: each set's directions, then each set's hit points
  *   POSES        n triangles: tri0, trin0, tri1, trin1 (rt_temporal_set_motion's pose per history frame)
  *   TRI_FRAMES   n = W * H pixels: tf0, tf1, tf2 (its int32 triangle frame per guide pair)
+ *   VARIANCE     n = W * H pixels: st0, st1 (rt_variance_set's state texel per history frame), tvar, dvar0, dvar1
  * scalars[8]: the allocation's total first, unused entries 0. */
 enum { RTS_LAYOUT_PATH_STATE = 0, RTS_LAYOUT_QUERY, RTS_LAYOUT_DENOISE, RTS_LAYOUT_HISTORY, RTS_LAYOUT_FRAME_TABLE,
-       RTS_LAYOUT_CAMERA_TABLE, RTS_LAYOUT_POSES, RTS_LAYOUT_TRI_FRAMES };
+       RTS_LAYOUT_CAMERA_TABLE, RTS_LAYOUT_POSES, RTS_LAYOUT_TRI_FRAMES, RTS_LAYOUT_VARIANCE };
 typedef struct rts_dev_span {
   uint64_t off, bytes;
   int32_t host, live;

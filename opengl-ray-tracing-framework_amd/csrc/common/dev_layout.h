@@ -219,6 +219,24 @@ inline TriFrames tri_frames(size_t npx) {
   return L;
 }
 
+// The variance mode of the display chain (rt_variance_set; rt_ctx::Variance), one allocation of its own
+// that exists only while the mode is on (the frame's size: dropped by rt_resize).  st[k]: the state
+// texel {l_prev, S_prev, v, m} beside each {r, g, b, n} texel of History's col[k].  tvar: the variance
+// of the temporal stage's output; dvar: the denoiser's ping-pong pair.  44 B per pixel.
+struct Variance {
+  Span st[2], tvar, dvar[2];
+  size_t total = 0;
+};
+inline Variance variance(size_t npx) {
+  Variance L;
+  Builder b;
+  for (Span& s : L.st) s = b.add(npx * 16);
+  L.tvar = b.add(npx * 4);
+  for (Span& v : L.dvar) v = b.add(npx * 4);
+  L.total = b.total();
+  return L;
+}
+
 // ---- frame table (rt_ctx::FrameTable), in ints ---------------------------------------------------
 // [cap] loop_num, [cap] rand_origin, then what wf_sobol adds: [cap][4] float2 Sobol pairs and [cap]
 // float2 blend weights.  The pinned host copy holds the two uploaded sub-tables alone.

@@ -24,6 +24,10 @@
 //                one residue class (x mod s, y mod s) per block, where the taps are dense (s >= 8)
 //   dn_atrous_direct  global reads of the 25 taps, served by L2 and the Infinity Cache (s = 4;
 //                which form serves which s >= 4 was measured: rt_render.hip dn_far_lds)
+//
+// The variance mode (rt_abi.h rt_variance_*; tests/variance_model.py) runs dn_var_spatial once and
+// then the *_var forms of the same two stagings for the same s: the colour term follows the variance
+// of what is filtered, which every iteration carries on beside the colour.
 #pragma once
 #include "rt_device.h"
 
@@ -63,6 +67,17 @@ RTD float dn_k(float r, float g, float b) {
   const float lum = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
   return 1.0f / (1.0f + max_(lum, 0.0f));
 }
+
+RTD float dn_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
+// What the variance forms read beside DnIter (rt_variance_set; DESIGN.md §4, tests/variance_model.py):
+// the variance of the displayed luminance per pixel, -1 where it is unknown
+struct DnVar {
+  const float* __restrict__ vin;    // of the iteration's input
+  float* __restrict__ vout;         // of its output
+  float sl;                         // sigma_lum
+};
+constexpr float kVarEps = 1e-8f;    // keeps 0 * 1 / (sigma_lum * sqrt(0) + eps) = 0 on a constant frame
 
 // The centre pixel p of a filter footprint
 struct DnCentre {
@@ -117,13 +132,89 @@ RTD void dn_store(const DnIter& I, size_t q, const DnCentre& p, const f3& sum, f
   }
 }
 
+// The variance form's centre: its own variance vp (vm: known, the pixel takes the luminance term),
+// its luminance and kl = 1 / (sigma_lum * sqrt(g) + eps), g the 3 x 3 Gaussian of the variance over
+// the neighbours of the centre's material with a known one (dy = -1..1 outer, dx inner; global reads,
+// whatever the staging of the taps)
+struct DnVarCentre {
+  float vp, lp, kl;
+  bool vm;
+};
+RTD DnVarCentre dn_var_centre(const DnIter& I, const DnVar& V, const DnCentre& p, int px, int py) {
+  DnVarCentre v;
+  v.vp = V.vin[(size_t)py * (size_t)I.W + (size_t)px];
+  v.vm = p.M != -1 && v.vp >= 0.0f;
+  v.lp = dn_lum(p.c.x, p.c.y, p.c.z);
+  v.kl = 0.0f;
+  if (v.vm) {
+    float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+      const int qy = py + dy;
+      if (qy < 0 || qy >= I.H) continue;
+#pragma unroll
+      for (int dx = -1; dx <= 1; dx++) {
+        const int qx = px + dx;
+        if (qx < 0 || qx >= I.W) continue;
+        const size_t qi = (size_t)qy * (size_t)I.W + (size_t)qx;
+        const float vq = V.vin[qi];
+        const float w = (dy ? 0.25f : 0.5f) * (dx ? 0.25f : 0.5f);
+        if (__float_as_int(I.g0[qi].w) == p.M && vq >= 0.0f) {
+          gs = gs + vq * w;
+          gw = gw + w;
+        }
+      }
+    }
+    v.kl = 1.0f / (V.sl * sqrtf(gs / gw) + kVarEps);
+  }
+  return v;
+}
+
+// dn_tap with the colour term |l_p - l_q| * kl where the centre's variance is known, and the tap's
+// share of the output's variance
+RTD void dn_tap_var(const DnIter& I, const DnCentre& p, const DnVarCentre& v, float4 cq, float4 aq, float4 bq, float vq, float hw,
+                    f3& sum, float& sw, float& s2) {
+  const float dnx = p.a.x - aq.x, dny = p.a.y - aq.y, dnz = p.a.z - aq.z;
+  const float dn2 = (dnx * dnx + dny * dny) + dnz * dnz;
+  const float dpx = bq.x - p.b.x, dpy = bq.y - p.b.y, dpz = bq.z - p.b.z;
+  const float d = ((p.a.x * dpx + p.a.y * dpy) + p.a.z * dpz) * p.b.w;
+  float ec;
+  if (v.vm) {
+    ec = fabsf(v.lp - dn_lum(cq.x, cq.y, cq.z)) * v.kl;
+  } else {
+    const float dcx = p.G.x - cq.x * cq.w, dcy = p.G.y - cq.y * cq.w, dcz = p.G.z - cq.z * cq.w;
+    ec = ((dcx * dcx + dcy * dcy) + dcz * dcz) * I.kc;
+  }
+  const float e = (dn2 * I.kn + (d * d) * I.kp) + (p.fin ? ec : 0.0f);
+  const float w = exp_(-e) * hw;
+  if (__float_as_int(aq.w) == p.M && dn_finite(cq) && w > 0.0f) {
+    sum.x = sum.x + cq.x * w;
+    sum.y = sum.y + cq.y * w;
+    sum.z = sum.z + cq.z * w;
+    sw = sw + w;
+    if (vq >= 0.0f) s2 = s2 + (w * w) * vq;
+  }
+}
+
+// dn_store, and the output's variance: sum(w^2 var_q) / sw^2 where the centre's was known and any
+// tap contributed, else the centre's own
+RTD void dn_store_var(const DnIter& I, const DnVar& V, size_t q, const DnCentre& p, const DnVarCentre& v, const f3& sum, float sw,
+                      float s2) {
+  dn_store(I, q, p, sum, sw);
+  V.vout[q] = (sw > 0.0f && v.vm) ? s2 / (sw * sw) : v.vp;
+}
+
 // cs = 1: dense tiles, taps STEP apart (s = STEP).  cs = s (STEP = 1): blockIdx.z is the residue
 // class (rx, ry) = (z % cs, z / cs) and the tile lies in the class's own coordinates,
 // frame pixel = (rx + cs * cx, ry + cs * cy).
-template <int STEP>
-__global__ __launch_bounds__(256) void dn_atrous_lds(const DnIter I, int cs) {
+// VAR: the variance form stages one more float per texel in an LDS array of its own (a wave's
+// ds_read_b32 of a tap is two rows of 32 consecutive floats: conflict-free) and leaves the 16-byte
+// texels of sC, sA, sB and their conflict-free argument as they are
+template <int STEP, bool VAR>
+RTD void dn_atrous_lds_body(const DnIter& I, int cs, const DnVar* V) {
   constexpr int HALO = 2 * STEP, PW = kDnTW + 2 * HALO, PH = kDnTH + 2 * HALO;
   __shared__ dn_v4 sC[PH * PW], sA[PH * PW], sB[PH * PW];
+  __shared__ float sV[VAR ? PH * PW : 1];
   // (the class is the slowest grid index: with rx fastest, so that the cs blocks that read the
   // same cache lines are dispatched together, 1080p took 0.62 ms instead of 0.41)
   const int rx = (int)blockIdx.z % cs, ry = (int)blockIdx.z / cs;
@@ -140,6 +231,9 @@ __global__ __launch_bounds__(256) void dn_atrous_lds(const DnIter I, int cs) {
       c = I.cin[q];
       a = I.g0[q];
       b = I.g1[q];
+      if (VAR) sV[i] = V->vin[q];
+    } else if (VAR) {
+      sV[i] = -1.0f;
     }
     dn_lds_put(sC, i, c);
     dn_lds_put(sA, i, a);
@@ -153,6 +247,24 @@ __global__ __launch_bounds__(256) void dn_atrous_lds(const DnIter I, int cs) {
   const DnCentre p = dn_centre(dn_lds_get(sC, ci), dn_lds_get(sA, ci), dn_lds_get(sB, ci));
   f3 sum = mk3(0.0f, 0.0f, 0.0f);
   float sw = 0.0f;
+  if (VAR) {
+    const int fx = rx + cs * cx, fy = ry + cs * cy;
+    const DnVarCentre v = dn_var_centre(I, *V, p, fx, fy);
+    float s2 = 0.0f;
+    if (p.M != -1) {
+#pragma unroll
+      for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+          const int qi = ci + dy * STEP * PW + dx * STEP;
+          dn_tap_var(I, p, v, dn_lds_get(sC, qi), dn_lds_get(sA, qi), dn_lds_get(sB, qi), sV[qi], dn_h(dy + 2) * dn_h(dx + 2), sum,
+                     sw, s2);
+        }
+      }
+    }
+    dn_store_var(I, *V, (size_t)fy * (size_t)I.W + (size_t)fx, p, v, sum, sw, s2);
+    return;
+  }
   if (p.M != -1) {
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
@@ -164,6 +276,15 @@ __global__ __launch_bounds__(256) void dn_atrous_lds(const DnIter I, int cs) {
     }
   }
   dn_store(I, (size_t)(ry + cs * cy) * (size_t)I.W + (size_t)(rx + cs * cx), p, sum, sw);
+}
+
+template <int STEP>
+__global__ __launch_bounds__(256) void dn_atrous_lds(const DnIter I, int cs) {
+  dn_atrous_lds_body<STEP, false>(I, cs, nullptr);
+}
+template <int STEP>
+__global__ __launch_bounds__(256) void dn_atrous_lds_var(const DnIter I, int cs, const DnVar V) {
+  dn_atrous_lds_body<STEP, true>(I, cs, &V);
 }
 
 __global__ __launch_bounds__(256) void dn_atrous_direct(const DnIter I) {
@@ -188,6 +309,74 @@ __global__ __launch_bounds__(256) void dn_atrous_direct(const DnIter I) {
     }
   }
   dn_store(I, pi, p, sum, sw);
+}
+
+__global__ __launch_bounds__(256) void dn_atrous_direct_var(const DnIter I, const DnVar V) {
+  const int px = (int)blockIdx.x * kDnTW + ((int)threadIdx.x & 31), py = (int)blockIdx.y * kDnTH + ((int)threadIdx.x >> 5);
+  if (px >= I.W || py >= I.H) return;
+  const size_t pi = (size_t)py * (size_t)I.W + (size_t)px;
+  const DnCentre p = dn_centre(I.cin[pi], I.g0[pi], I.g1[pi]);
+  const DnVarCentre v = dn_var_centre(I, V, p, px, py);
+  f3 sum = mk3(0.0f, 0.0f, 0.0f);
+  float sw = 0.0f, s2 = 0.0f;
+  if (p.M != -1) {
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+      const int qy = py + I.s * dy;
+      if (qy < 0 || qy >= I.H) continue;
+#pragma unroll
+      for (int dx = -2; dx <= 2; dx++) {
+        const int qx = px + I.s * dx;
+        if (qx < 0 || qx >= I.W) continue;
+        const size_t qi = (size_t)qy * (size_t)I.W + (size_t)qx;
+        dn_tap_var(I, p, v, I.cin[qi], I.g0[qi], I.g1[qi], V.vin[qi], dn_h(dy + 2) * dn_h(dx + 2), sum, sw, s2);
+      }
+    }
+  }
+  dn_store_var(I, V, pi, p, v, sum, sw, s2);
+}
+
+// The spatial estimate of the variance mode, before the first iteration: vout = src (nullptr: all
+// unknown), and where a hit pixel's is unknown the variance of luminance over the 7 x 7 neighbours
+// on its surface (the centre's material, finite, |dN|^2 <= sn2, |N . dP| / t <= sp: the temporal
+// stage's test), in one pass over the differences from the centre's luminance (0 when that is not
+// finite); fewer than two such neighbours leave it unknown.  dy = -3..3 outer, dx inner.
+__global__ __launch_bounds__(256) void dn_var_spatial(const DnIter I, const float* __restrict__ src, float* __restrict__ vout,
+                                                      float sn2, float sp) {
+  const int px = (int)blockIdx.x * kDnTW + ((int)threadIdx.x & 31), py = (int)blockIdx.y * kDnTH + ((int)threadIdx.x >> 5);
+  if (px >= I.W || py >= I.H) return;
+  const size_t pi = (size_t)py * (size_t)I.W + (size_t)px;
+  float var = src ? src[pi] : -1.0f;
+  const float4 a = I.g0[pi];
+  const int M = __float_as_int(a.w);
+  if (M != -1 && var < 0.0f) {
+    const float4 c = I.cin[pi], b = I.g1[pi];
+    const float ref = dn_finite(c) ? dn_lum(c.x, c.y, c.z) : 0.0f;
+    float s1 = 0.0f, s2 = 0.0f, cnt = 0.0f;
+    for (int dy = -3; dy <= 3; dy++) {
+      const int qy = py + dy;
+      if (qy < 0 || qy >= I.H) continue;
+#pragma unroll
+      for (int dx = -3; dx <= 3; dx++) {
+        const int qx = px + dx;
+        if (qx < 0 || qx >= I.W) continue;
+        const size_t qi = (size_t)qy * (size_t)I.W + (size_t)qx;
+        const float4 cq = I.cin[qi], aq = I.g0[qi], bq = I.g1[qi];
+        const float nx = a.x - aq.x, ny = a.y - aq.y, nz = a.z - aq.z;
+        const float dn2 = (nx * nx + ny * ny) + nz * nz;
+        const float qx_ = bq.x - b.x, qy_ = bq.y - b.y, qz_ = bq.z - b.z;
+        const float d = (a.x * qx_ + a.y * qy_) + a.z * qz_;
+        if (__float_as_int(aq.w) == M && dn_finite(cq) && dn2 <= sn2 && fabsf(d) * b.w <= sp) {
+          const float dl = dn_lum(cq.x, cq.y, cq.z) - ref;
+          s1 = s1 + dl;
+          s2 = s2 + dl * dl;
+          cnt = cnt + 1.0f;
+        }
+      }
+    }
+    if (cnt >= 2.0f) var = max_((s2 - (s1 * s1) / cnt) / (cnt - 1.0f), 0.0f);
+  }
+  vout[pi] = var;
 }
 
 // tiles: the accumulation (world == 1: local tile = global tile), or frame: W*H*3 floats.  hits:

@@ -281,6 +281,17 @@ struct rt_ctx {
     int* tf[3] = {nullptr, nullptr, nullptr};
     bool tf_valid[3] = {false, false, false};  // the pair's guides were packed with its triangle frame
   } mo;
+  // The variance mode of the display chain (rt_variance_set; dvl::Variance): nothing of it exists
+  // while the mode is off.  State frame k goes with tp.col[k], like Motion's pose slot.
+  struct Variance {
+    rt_variance_params p{0, 1.5f, 64, 0};  // survives rt_set_scene and rt_resize
+    void* mem = nullptr;                  // for W*H pixels: freed by a resize
+    float4* st[2] = {nullptr, nullptr};   // {l_prev, S_prev, v, m} beside tp.col[k]
+    float* tvar = nullptr;                // the variance of tp.out
+    float* dvar[2] = {nullptr, nullptr};  // the denoiser's ping-pong pair
+    bool tvar_valid = false;              // tvar describes what tp.out holds
+    const float* last = nullptr;          // the last output's variance (rt_variance_frame)
+  } vr;
 };
 
 namespace {
@@ -717,6 +728,14 @@ void motion_free_frames(rt_ctx* c) {
   m.tf_mem = nullptr;
   for (bool& v : m.tf_valid) v = false;
 }
+// The variance mode's allocation (rt_ctx::Variance), the setting kept
+void variance_free(rt_ctx* c) {
+  rt_ctx::Variance& v = c->vr;
+  if (v.mem) (void)hipFree(v.mem);
+  v.mem = nullptr;
+  v.tvar_valid = false;
+  v.last = nullptr;
+}
 
 // ---- rt_update_geometry (rt_geometry.h; the definition is scn::update_geometry)
 // The refit schedule and the reduction cell, on the first update after a rt_set_scene: the node
@@ -834,6 +853,7 @@ int rt_destroy(rt_ctx* c) {
   if (c->tp.mem) (void)hipFree(c->tp.mem);
   motion_free_poses(c);
   motion_free_frames(c);
+  variance_free(c);
   dfree(c->d_disp);
   dfree(c->d_gather);
   for (auto& m : c->rccl_comms) (void)ncclCommDestroy(m);
@@ -865,6 +885,8 @@ int rt_set_scene(rt_ctx* c, const rt_scene_soa* s) {
   // without one (renders and queries then refuse) rather than with a mix of old and new buffers
   c->scene_set = false;
   c->tp.drop();  // the display history shows another scene
+  c->vr.tvar_valid = false;  // (and so do the variance frames)
+  c->vr.last = nullptr;
   motion_free_poses(c);  // (its poses are another triangle list's)
   c->mo.gen = 0;
   geo_drop(c);   // and the refit schedule is another tree's
@@ -1107,6 +1129,7 @@ static int apply_tiling(rt_ctx* c, int width, int height, const rt_tiling& tl, s
   if (c->tp.mem) (void)hipFree(c->tp.mem);  // and so is the display history
   c->tp = rt_ctx::Temporal{};
   motion_free_frames(c);  // and its triangle frames
+  variance_free(c);       // and the variance mode's frames
   c->W = width; c->H = height;
   c->tile_w = tl.tile_w; c->tile_h = tl.tile_h; c->rank = tl.rank; c->world = tl.world;
   c->tiles_x = (width + tl.tile_w - 1) / tl.tile_w;
@@ -2675,6 +2698,20 @@ int reserve_poses(rt_ctx* c) {
   return RT_OK;
 }
 
+// The variance mode's frames for the current frame size (the mode is on)
+int reserve_variance(rt_ctx* c) {
+  rt_ctx::Variance& v = c->vr;
+  if (v.mem) return RT_OK;
+  const dvl::Variance L = dvl::variance((size_t)c->W * c->H);
+  if (int rc = alloc_block(c, v.mem, L.total, "variance frames do not fit in device memory")) return rc;
+  for (int k = 0; k < 2; k++) place(v.st[k], v.mem, L.st[k]);
+  place(v.tvar, v.mem, L.tvar);
+  for (int k = 0; k < 2; k++) place(v.dvar[k], v.mem, L.dvar[k]);
+  v.tvar_valid = false;
+  v.last = nullptr;
+  return RT_OK;
+}
+
 // The guide pair dn.g0 / dn.g1 point at (0, the denoiser's own, without a display history)
 int tp_current_pair(const rt_ctx* c) {
   for (int k = 1; k < 3; k++)
@@ -2780,6 +2817,9 @@ int rt_denoise_async(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_para
   if (int rc = display_state(c, fp, reuse, trace, "no guides of an earlier denoise call for this size")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = reserve_denoise(c)) return rc;
+  const bool var_mode = c->vr.p.on != 0;
+  if (var_mode)
+    if (int rc = reserve_variance(c)) return rc;
   rt_ctx::Denoise& d = c->dn;
   int pair;  // (a live candidate of the display history keeps its guides)
   if (int rc = display_pack(c, fp, reuse, frame_in_device, hits_dev, true, pair)) return rc;
@@ -2791,6 +2831,23 @@ int rt_denoise_async(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_para
   I.kn = 1.0f / (dp->sigma_normal * dp->sigma_normal);
   I.kp = 1.0f / (dp->sigma_plane * dp->sigma_plane);
   I.kc = 1.0f / (dp->sigma_color * dp->sigma_color);
+  auto tiles_of = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
+  rt_ctx::Variance& vr = c->vr;
+  rtd::DnVar V{};
+  if (var_mode) {
+    // The input's variance: the temporal stage's when the input is its output, else unknown; the
+    // spatial estimate fills what is unknown
+    const float* src = (frame_in_device && frame_in_device == c->tp.out && c->tp.cand >= 0 && vr.tvar_valid) ? vr.tvar : nullptr;
+    I.cin = d.col[0];
+    I.cout = nullptr;
+    I.out3 = nullptr;
+    I.s = 1;
+    const dim3 grid(tiles_of(c->W, rtd::kDnTW), tiles_of(c->H, rtd::kDnTH), 1);
+    hipLaunchKernelGGL(rtd::dn_var_spatial, grid, dim3(256), 0, c->stream, I, src, vr.dvar[0],
+                       dp->sigma_normal * dp->sigma_normal, dp->sigma_plane);
+    HIPCHK(c, hipGetLastError());
+    V.sl = vr.p.sigma_lum;
+  }
   for (int i = 0; i < dp->iterations; i++) {
     const bool last = i + 1 == dp->iterations;
     const int s = 1 << i;
@@ -2798,8 +2855,22 @@ int rt_denoise_async(rt_ctx* c, const rt_frame_params* fp, const rt_denoise_para
     I.cout = last ? nullptr : d.col[(i + 1) & 1];
     I.out3 = last ? d.out : nullptr;
     I.s = s;
-    auto tiles_of = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
-    if (s <= 2) {
+    if (var_mode) {  // the same forms for the same s, with the variance beside the colour
+      V.vin = vr.dvar[i & 1];
+      V.vout = vr.dvar[(i + 1) & 1];
+      if (s <= 2) {
+        const dim3 grid(tiles_of(c->W, rtd::kDnTW), tiles_of(c->H, rtd::kDnTH), 1);
+        if (s == 1) hipLaunchKernelGGL(rtd::dn_atrous_lds_var<1>, grid, dim3(256), 0, c->stream, I, 1, V);
+        else hipLaunchKernelGGL(rtd::dn_atrous_lds_var<2>, grid, dim3(256), 0, c->stream, I, 1, V);
+      } else if (dn_far_lds(s)) {
+        const dim3 grid(tiles_of((c->W + s - 1) / s, rtd::kDnTW), tiles_of((c->H + s - 1) / s, rtd::kDnTH), (unsigned)(s * s));
+        hipLaunchKernelGGL(rtd::dn_atrous_lds_var<1>, grid, dim3(256), 0, c->stream, I, s, V);
+      } else {
+        const dim3 grid(tiles_of(c->W, rtd::kDnTW), tiles_of(c->H, rtd::kDnTH), 1);
+        hipLaunchKernelGGL(rtd::dn_atrous_direct_var, grid, dim3(256), 0, c->stream, I, V);
+      }
+      vr.last = V.vout;
+    } else if (s <= 2) {
       const dim3 grid(tiles_of(c->W, rtd::kDnTW), tiles_of(c->H, rtd::kDnTH), 1);
       if (s == 1) hipLaunchKernelGGL(rtd::dn_atrous_lds<1>, grid, dim3(256), 0, c->stream, I, 1);
       else hipLaunchKernelGGL(rtd::dn_atrous_lds<2>, grid, dim3(256), 0, c->stream, I, 1);
@@ -2856,8 +2927,13 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
   if (int rc = reserve_temporal(c)) return rc;
   if (c->mo.on)
     if (int rc = reserve_poses(c)) return rc;
+  const bool var_mode = c->vr.p.on != 0;
+  if (var_mode)
+    if (int rc = reserve_variance(c)) return rc;
   rt_ctx::Denoise& d = c->dn;
   rt_ctx::Temporal& t = c->tp;
+  // (variance mode) this call overwrites the previous call's candidate in place: the same view
+  const bool own = t.cand >= 0 && !(tp->flags & (RT_TEMPORAL_RESET | RT_TEMPORAL_ADVANCE));
   // The previous output changes roles: the history (ADVANCE), or nothing (this call's replaces it)
   if (tp->flags & RT_TEMPORAL_RESET) {
     t.drop();
@@ -2892,6 +2968,14 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
   T.sp = tp->sigma_plane;
   const dim3 grid((unsigned)((c->W + rtd::kDnTW - 1) / rtd::kDnTW), (unsigned)((c->H + rtd::kDnTH - 1) / rtd::kDnTH));
   rt_ctx::Motion& m = c->mo;
+  rtd::TpVar V{};
+  if (var_mode) {
+    V.hst = t.hist >= 0 ? c->vr.st[t.hist] : nullptr;
+    V.st = c->vr.st[cand];
+    V.var = c->vr.tvar;
+    V.own = own ? 1 : 0;
+    V.max_m = (float)c->vr.p.max_estimates;
+  }
   // The motion form only where the history was made from another pose than the current one
   if (m.on && t.hist >= 0 && t.pose_gen[t.hist] >= 0 && t.pose_gen[t.hist] != m.gen) {
     rtd::TpMotion Mo;
@@ -2901,11 +2985,18 @@ int rt_temporal_async(rt_ctx* c, const rt_frame_params* fp, const rt_temporal_pa
     Mo.htri = m.tri[t.hist];
     Mo.htrin = m.trin[t.hist];
     Mo.n_tri = c->n_tri;
-    hipLaunchKernelGGL(rtd::tp_resolve_motion, grid, dim3(256), 0, c->stream, T, Mo);
+    if (var_mode) hipLaunchKernelGGL(rtd::tp_resolve_motion_var, grid, dim3(256), 0, c->stream, T, Mo, V);
+    else hipLaunchKernelGGL(rtd::tp_resolve_motion, grid, dim3(256), 0, c->stream, T, Mo);
+  } else if (var_mode) {
+    hipLaunchKernelGGL(rtd::tp_resolve_var, grid, dim3(256), 0, c->stream, T, V);
   } else {
     hipLaunchKernelGGL(rtd::tp_resolve, grid, dim3(256), 0, c->stream, T);
   }
   HIPCHK(c, hipGetLastError());
+  if (var_mode) {
+    c->vr.tvar_valid = true;
+    c->vr.last = c->vr.tvar;
+  }
   // The candidate was made from the current pose: its slot holds it, copied once per generation
   if (m.on && t.pose_gen[cand] != m.gen) {
     const size_t bytes = (size_t)c->n_tri * dvl::kTriRecBytes;
@@ -2958,6 +3049,45 @@ int rt_temporal_history(rt_ctx* c, float* n_out_host) {
   HIPCHK(c, hipMemcpyAsync(buf.data(), c->tp.col[c->tp.cand], npx * 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < npx; i++) n_out_host[i] = buf[4 * i + 3];
+  return RT_OK;
+}
+
+// ----------------------------------------------------------------------------- variance mode
+int rt_variance_default_params(rt_variance_params* vp) {
+  if (!vp) return RT_ERR_ARG;
+  *vp = rt_ctx::Variance{}.p;
+  return RT_OK;
+}
+
+int rt_variance_set(rt_ctx* c, const rt_variance_params* vp) {
+  if (!c) return RT_ERR_ARG;
+  if (!vp) return fail(c, RT_ERR_ARG, "null parameters");
+  if (vp->on != 0 && vp->on != 1) return fail(c, RT_ERR_ARG, "on is 0 or 1");
+  if (!dn_sigma_ok(vp->sigma_lum)) return fail(c, RT_ERR_ARG, "sigma_lum is not finite and > 0");
+  if (vp->max_estimates < 1) return fail(c, RT_ERR_ARG, "max_estimates < 1");
+  if (vp->flags != 0) return fail(c, RT_ERR_ARG, "unknown flags");
+  if (int rc = rt_synchronize(c)) return rc;  // (a display stage in flight reads the buffers freed below)
+  c->tp.drop();  // (a history made outside the mode has no state texels)
+  c->vr.tvar_valid = false;
+  c->vr.last = nullptr;
+  if (!vp->on) variance_free(c);
+  c->vr.p = *vp;
+  return RT_OK;
+}
+
+int rt_variance_get(const rt_ctx* c, rt_variance_params* vp) {
+  if (!c || !vp) return RT_ERR_ARG;
+  *vp = c->vr.p;
+  return RT_OK;
+}
+
+int rt_variance_frame(rt_ctx* c, float* var_out_host) {
+  if (!c) return RT_ERR_ARG;
+  if (!var_out_host) return fail(c, RT_ERR_ARG, "null output");
+  if (!c->vr.p.on || !c->vr.mem || !c->vr.last) return fail(c, RT_ERR_STATE, "no temporal or denoise call in the variance mode for the current size");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(var_out_host, c->vr.last, (size_t)c->W * c->H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
 

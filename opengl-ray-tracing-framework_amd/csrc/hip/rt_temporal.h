@@ -14,6 +14,10 @@
 //                LDS: the 2 x 2 footprints of neighbouring lanes overlap and L2 serves them.
 //                Writes the candidate {r, g, b, n_out} and the W*H*3 output frame in the same pass.
 //
+//   tp_resolve_var, tp_resolve_motion_var   the same body in the variance mode (rt_variance_set): one
+//                more 16-byte texel {l_prev, S_prev, v, m} per history tap and per output pixel, and
+//                the variance of the displayed luminance as a W*H frame (tests/variance_model.py)
+//
 // The arithmetic is fixed (tests/temporal_model.py restates it in numpy): every
 // step is one correctly rounded fp32 operation in the order written below; taps run j = 0..1
 // outer (rows), i = 0..1 inner.  There are no transcendentals, and floor is exact.
@@ -107,10 +111,23 @@ RTD bool tp_moved(const TpMotion& m, int t, TpV3& P, TpV3& N, bool& ok) {
   return true;
 }
 
+// What the variance forms read and write beside TpCall (rt_variance_set; DESIGN.md §4,
+// tests/variance_model.py): one state texel {l_prev, S_prev, v, m} beside each {r, g, b, n} texel of
+// the history and of the candidate: the luminance and sample count of the last input seen for the
+// view, the running mean of the per-sample luminance variance estimates and their number
+struct TpVar {
+  const float4* __restrict__ hst;   // the history's state texels (read where hc is)
+  float4* st;                       // the candidate's: read first when `own`, then written
+  float* __restrict__ var;          // this call's variance of the displayed luminance; -1: unknown
+  int own;                          // st holds the previous call's state of the same view (no ADVANCE since)
+  float max_m;                      // cap of m
+};
+
 // MOTION = false is tp_resolve as it always was; with MOTION a pixel of a moved triangle enters the
-// same statements with the history pose's P and N in place of its own.
-template <bool MOTION>
-RTD void tp_resolve_px(const TpCall& T, const TpMotion* mo) {
+// same statements with the history pose's P and N in place of its own.  VAR adds the variance
+// state: v and m ride the colour's taps, and the tail below the blend updates them.
+template <bool MOTION, bool VAR>
+RTD void tp_resolve_px(const TpCall& T, const TpMotion* mo, const TpVar* V) {
   const int px = (int)blockIdx.x * kDnTW + ((int)threadIdx.x & 31), py = (int)blockIdx.y * kDnTH + ((int)threadIdx.x >> 5);
   if (px >= T.W || py >= T.H) return;
   const size_t pi = (size_t)py * (size_t)T.W + (size_t)px;
@@ -118,8 +135,11 @@ RTD void tp_resolve_px(const TpCall& T, const TpMotion* mo) {
   const int M = __float_as_int(a.w);
   const bool fin = dn_finite(c);
   float r = c.x, g = c.y, b = c.z, n = 0.0f;  // a miss, or a non-finite input without history
+  float4 st = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (VAR) a miss keeps no state
+  float var = -1.0f;
   if (M != -1) {
     float sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f, sw = 0.0f;
+    float sv = 0.0f, sm = 0.0f, lh = 0.0f, hn_ = 0.0f;  // (VAR)
     if (T.hc) {
       const float4 p = T.g1[pi];
       TpV3 P{p.x, p.y, p.z}, N{a.x, a.y, a.z};
@@ -159,6 +179,11 @@ RTD void tp_resolve_px(const TpCall& T, const TpMotion* mo) {
                 sg = sg + cq.y * w;
                 sb = sb + cq.z * w;
                 sn = sn + cq.w * w;
+                if (VAR) {
+                  const float4 sq = V->hst[qi];
+                  sv = sv + sq.z * w;
+                  sm = sm + sq.w * w;
+                }
                 sw = sw + w;
               }
             }
@@ -177,17 +202,60 @@ RTD void tp_resolve_px(const TpCall& T, const TpMotion* mo) {
       } else {
         r = hr; g = hg; b = hb; n = hn;
       }
+      if (VAR) {
+        lh = dn_lum(hr, hg, hb);
+        hn_ = hn;
+      }
     } else if (fin) {
       n = min_(T.S, T.max_n);
+    }
+    if (VAR) {
+      // One estimate e of the per-sample variance, a squared difference of two independent means:
+      // the still view's new samples against its earlier ones (Welford's chunk-merge term), or
+      // this input against the reprojected history
+      const float lc = dn_lum(c.x, c.y, c.z);
+      float lp = 0.0f, Sp = 0.0f, v0, m0, e;
+      bool upd;
+      if (V->own) {
+        const float4 o = V->st[pi];
+        lp = o.x; Sp = o.y; v0 = o.z; m0 = o.w;
+        const float dS = T.S - Sp;
+        const float s = (T.S * lc - Sp * lp) / dS;
+        const float d = s - lp;
+        e = (d * d) * ((dS * Sp) / T.S);
+        upd = fin && T.S > Sp && Sp > 0.0f;
+      } else {
+        const bool has = sw > 0.0f;
+        v0 = has ? sv / sw : 0.0f;
+        m0 = has ? sm / sw : 0.0f;
+        const float d = lc - lh;
+        e = (d * d) / (1.0f / T.S + 1.0f / hn_);
+        upd = has && fin;
+      }
+      upd = upd && isfinite(e);
+      const float m1 = m0 + 1.0f;
+      const float v1 = v0 + (e - v0) / m1;
+      st = make_float4(fin ? lc : lp, fin ? T.S : Sp, upd ? v1 : v0, upd ? min_(m1, V->max_m) : m0);
+      if (st.w > 0.0f) var = st.z / max_(n, T.S);
     }
   }
   T.cand[pi] = make_float4(r, g, b, n);
   float* o = T.out3 + 3 * pi;
   o[0] = r; o[1] = g; o[2] = b;
+  if (VAR) {
+    V->st[pi] = st;
+    V->var[pi] = var;
+  }
 }
 
-__global__ __launch_bounds__(256) void tp_resolve(const TpCall T) { tp_resolve_px<false>(T, nullptr); }
-__global__ __launch_bounds__(256) void tp_resolve_motion(const TpCall T, const TpMotion Mo) { tp_resolve_px<true>(T, &Mo); }
+__global__ __launch_bounds__(256) void tp_resolve(const TpCall T) { tp_resolve_px<false, false>(T, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void tp_resolve_motion(const TpCall T, const TpMotion Mo) {
+  tp_resolve_px<true, false>(T, &Mo, nullptr);
+}
+__global__ __launch_bounds__(256) void tp_resolve_var(const TpCall T, const TpVar V) { tp_resolve_px<false, true>(T, nullptr, &V); }
+__global__ __launch_bounds__(256) void tp_resolve_motion_var(const TpCall T, const TpMotion Mo, const TpVar V) {
+  tp_resolve_px<true, true>(T, &Mo, &V);
+}
 
 // The triangle frame of a fresh pack on a context in motion mode (the guide texels do not hold the
 // triangle index): T of the rt_hit records in local-tile order, or -1 for a miss, in frame order

@@ -1381,6 +1381,12 @@ int rts_dev_layout(int32_t kind, uint64_t n, uint64_t m, uint64_t* scalars, rts_
       for (dvl::Span at : L.tf) put(at, 0, -1, true);
       break;
     }
+    case RTS_LAYOUT_VARIANCE: {
+      const dvl::Variance L = dvl::variance(n);
+      scalars[0] = L.total;
+      for (dvl::Span at : {L.st[0], L.st[1], L.tvar, L.dvar[0], L.dvar[1]}) put(at, 0, -1, true);
+      break;
+    }
     default: return RTS_ERR_ARG;
   }
   *n_spans = k;

@@ -118,6 +118,7 @@ class Settings:
     enable_denoise: bool = False  # (no counterpart in the reference) rt_denoise before the display pass
     enable_temporal: bool = False  # (likewise) rt_temporal before both: the display history follows the camera
     enable_temporal_motion: bool = False  # rt_temporal_set_motion: and the triangles Input.geometry moved
+    enable_variance: bool = False  # rt_variance_set: both stages follow the estimated variance (a converged view stays sharp)
 
 
 # OnGUI controls that restart the accumulation (main.cpp:343-368, :408); tone mapping / gamma
@@ -180,6 +181,7 @@ class Session:
         # stage was last on): the previous call's output becomes the history (RT_TEMPORAL_ADVANCE)
         self._advance = True
         self._motion = False  # the context's motion mode as this session last set it (Settings.enable_temporal_motion)
+        self._variance = False  # likewise the variance mode (Settings.enable_variance)
 
     # main.cpp:296-318
     def _mouse(self, xpos: float, ypos: float, rmb: bool) -> None:
@@ -229,6 +231,10 @@ class Session:
             self._motion = bool(self.settings.enable_temporal_motion)
             self.r.set_temporal_motion(self._motion)
             self._guides_current = False
+            self._advance = True
+        if bool(self.settings.enable_variance) != self._variance:  # (drops the display history too; the guides stay)
+            self._variance = bool(self.settings.enable_variance)
+            self.r.set_variance(self._variance)
             self._advance = True
         if inp.camera_position is not None:
             self.camera.position = np.array(inp.camera_position, f32)

@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "rt_denoise_default_params", "rt_denoise_async", "rt_denoise",
     "rt_temporal_default_params", "rt_temporal_async", "rt_temporal", "rt_temporal_history",
     "rt_temporal_set_motion", "rt_temporal_get_motion",
+    "rt_variance_default_params", "rt_variance_set", "rt_variance_get", "rt_variance_frame",
     "rt_update_geometry", "rt_update_geometry_device", "rt_scene_download", "rt_scene_array_bytes",
     "rt_scene_bounds",
 )
@@ -59,6 +60,7 @@ RT_HAS_DENOISE = 1
 RT_DENOISE_REUSE_GUIDES = 1
 RT_HAS_TEMPORAL = 1
 RT_HAS_TEMPORAL_MOTION = 1
+RT_HAS_VARIANCE = 1
 RT_HAS_GEOMETRY_UPDATE = 1
 # rt_scene_download's arrays and the dtype / row shape each comes back as
 SCENE_ARRAYS = ("tri", "trx", "trin", "hrec", "nodes", "qnodes")
@@ -229,6 +231,24 @@ class TemporalParams:
                                 float(self.sigma_plane), int(self.flags) | int(extra_flags))
 
 
+class RtVarianceParams(C.Structure):
+    _fields_ = [("on", C.c_int32), ("sigma_lum", C.c_float), ("max_estimates", C.c_int32), ("flags", C.c_int32)]
+
+
+@dataclasses.dataclass
+class VarianceParams:
+    """rt_variance_params with rt_variance_default_params' values: the mode's switch, the luminance
+    edge-stopping term in standard deviations of what the denoiser filters, and the cap of the
+    number of variance estimates a pixel's running mean counts."""
+    on: bool = False
+    sigma_lum: float = 1.5
+    max_estimates: int = 64
+    flags: int = 0
+
+    def to_c(self) -> RtVarianceParams:
+        return RtVarianceParams(1 if self.on else 0, float(self.sigma_lum), int(self.max_estimates), int(self.flags))
+
+
 _lib = None
 _variants: dict = {}
 
@@ -338,6 +358,12 @@ def _bind(L: C.CDLL) -> C.CDLL:
     if hasattr(L, "rt_temporal_set_motion"):  # RT_HAS_TEMPORAL_MOTION (likewise)
         L.rt_temporal_set_motion.argtypes = [vp, C.c_int32]
         L.rt_temporal_get_motion.argtypes = [vp, _i32p]
+    if hasattr(L, "rt_variance_set"):  # RT_HAS_VARIANCE (likewise)
+        vpp = C.POINTER(RtVarianceParams)
+        L.rt_variance_default_params.argtypes = [vpp]
+        L.rt_variance_set.argtypes = [vp, vpp]
+        L.rt_variance_get.argtypes = [vp, vpp]
+        L.rt_variance_frame.argtypes = [vp, _f32p]
     if hasattr(L, "rt_update_geometry"):  # RT_HAS_GEOMETRY_UPDATE (likewise)
         L.rt_update_geometry.argtypes = [vp, _i32p, C.c_int32, C.c_int32] + [_f32p] * 6
         L.rt_update_geometry_device.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 6
@@ -707,6 +733,26 @@ class Renderer:
         """rt_temporal_history: (H, W) float32 history lengths of the last temporal call's output."""
         out = np.zeros((self.height, self.width), np.float32)
         self._check(self._L.rt_temporal_history(self._h, _fp(out)), "rt_temporal_history")
+        return out
+
+    def set_variance(self, vp: "Optional[VarianceParams | bool]" = True) -> None:
+        """rt_variance_set: the variance mode of the display chain (True / False: the defaults with
+        the mode on / off).  Waits for the work in flight; drops the display history."""
+        if not isinstance(vp, VarianceParams):
+            vp = VarianceParams(on=bool(vp))
+        v = vp.to_c()
+        self._check(self._L.rt_variance_set(self._h, C.byref(v)), "rt_variance_set")
+
+    def get_variance(self) -> VarianceParams:
+        v = RtVarianceParams()
+        self._check(self._L.rt_variance_get(self._h, C.byref(v)), "rt_variance_get")
+        return VarianceParams(on=bool(v.on), sigma_lum=float(v.sigma_lum), max_estimates=int(v.max_estimates), flags=int(v.flags))
+
+    def variance_frame(self) -> np.ndarray:
+        """rt_variance_frame: (H, W) float32 variance of the displayed luminance of the last temporal or
+        denoise call's output in the variance mode; -1 where it is unknown."""
+        out = np.zeros((self.height, self.width), np.float32)
+        self._check(self._L.rt_variance_frame(self._h, _fp(out)), "rt_variance_frame")
         return out
 
     # ------------------------------------------------------------- ray queries

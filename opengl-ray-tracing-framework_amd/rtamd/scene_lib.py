@@ -370,7 +370,7 @@ def tri_filter(tri: np.ndarray):
 
 # rts_dev_layout's kinds and the names of their spans (one set's, for the path state), in order
 LAYOUT_KINDS = ("path_state", "query", "denoise", "history", "frame_table", "camera_table", "poses",
-                "tri_frames")
+                "tri_frames", "variance")
 _SLOT_NAMES = ("s0", "s1", "s2", "s3", "s4", "s5", "ra", "rb", "sa", "sb", "res", "fin", "queue0", "queue1",
                "active0", "active1", "queue_s0", "queue_s1", "hit", "cnt")
 _ROW_NAMES = ("s0", "s1", "s2", "s3", "s4", "s5", "ra", "rb", "sa", "sb", "res", "rpath")
@@ -382,6 +382,7 @@ LAYOUT_SPANS = {
     "frame_table": ("loop_num", "rand_origin", "sobol", "blend_w"),
     "poses": ("tri0", "trin0", "tri1", "trin1"),
     "tri_frames": ("tf0", "tf1", "tf2"),
+    "variance": ("st0", "st1", "tvar", "dvar0", "dvar1"),
 }
 
 

@@ -28,6 +28,9 @@ ap.add_argument("--config", default="C3")
 ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--height", type=int, default=1080)
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--variance", action="store_true",
+                help="the variance mode (rt_variance_set): no temporal stage runs here, so every call pays the 7 x 7 "
+                     "spatial estimate (tools/temporal_bench.py --variance times the chain that does not)")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "denoise_bench.jsonl"), help="'' = do not write")
 a = ap.parse_args()
 
@@ -45,6 +48,8 @@ r = Renderer(0)
 r.set_scene_soa(sd.soa, sd.nodes)
 r.set_env(*cf.load_env())
 r.resize(W, H)
+if a.variance:
+    r.set_variance(True)
 fp = cf.frame_params(W, H)
 ro = cf.rand_origins(2 * a.reps + 8)
 stream = torch.cuda.ExternalStream(r.stream)
@@ -64,7 +69,7 @@ def timed(call):
     return round(e0.elapsed_time(e1) / a.reps, 4)
 
 
-res = {"config": a.config, "width": W, "height": H, "reps": a.reps}
+res = {"config": a.config, "width": W, "height": H, "reps": a.reps, "variance": a.variance}
 res["denoise_fresh_ms"] = timed(lambda k: r.denoise_async(fp))
 res["denoise_reuse_ms"] = timed(lambda k: r.denoise_async(fp, reuse_guides=True))
 res["denoise_reuse_2it_ms"] = timed(lambda k: r.denoise_async(fp, DenoiseParams(iterations=2), reuse_guides=True))

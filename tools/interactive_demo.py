@@ -35,6 +35,8 @@ ap.add_argument("--temporal", action="store_true", help="Settings.enable_tempora
 ap.add_argument("--denoise", action="store_true", help="Settings.enable_denoise: the à-trous filter before the display pass")
 ap.add_argument("--motion", action="store_true",
                 help="Settings.enable_temporal_motion: the history also follows the triangles --spin turns")
+ap.add_argument("--variance", action="store_true",
+                help="Settings.enable_variance: both display stages follow the estimated variance (rt_variance_set)")
 ap.add_argument("--spin", action="store_true",
                 help="a phase with the config's last object turning under the still camera (Input.geometry: one "
                      "rt_update_geometry per frame)")
@@ -47,7 +49,7 @@ r = Renderer(0)
 r.set_scene_soa(sd.soa, sd.nodes)
 r.set_env(*cf.load_env())
 s = ia.Session(r, W, H, settings=ia.Settings(enable_temporal=a.temporal, enable_denoise=a.denoise,
-                                                  enable_temporal_motion=a.motion),
+                                                  enable_temporal_motion=a.motion, enable_variance=a.variance),
                frames_in_flight=a.in_flight)
 dt = 1.0 / 60.0
 phases = [

@@ -25,8 +25,13 @@ ap.add_argument("--no-tonemap", action="store_true", help="enableToneMapping off
 ap.add_argument("--no-gamma", action="store_true", help="enableGammaCorrection off")
 ap.add_argument("--brdf", action="store_true", help="enableBSDF off")
 ap.add_argument("--denoise", action="store_true", help="show the frame through rt_denoise (default parameters)")
+ap.add_argument("--variance", action="store_true",
+                help="with --denoise: the variance mode (rt_variance_set; one call without a temporal stage, so the "
+                     "7 x 7 spatial estimate of the variance guides the filter)")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
+if a.variance and not a.denoise:
+    ap.error("--variance goes with --denoise")
 
 cfg = cf.CONFIGS[a.config]
 W, H = a.width or cfg.width, a.height or cfg.height
@@ -40,6 +45,8 @@ t = time.time()
 st = r.render(fp, cf.rand_origins(a.spp))
 dt = time.time() - t
 flags = (0 if a.no_tonemap else RT_DISPLAY_TONEMAP) | (0 if a.no_gamma else RT_DISPLAY_GAMMA)
+if a.variance:
+    r.set_variance(True)
 img = r.tonemap(flags, frame_ptr=r.denoise_async(fp) if a.denoise else None)
 Path(a.out).parent.mkdir(parents=True, exist_ok=True)
 sl.write_png(a.out, img)

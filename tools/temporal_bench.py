@@ -30,6 +30,7 @@ ap.add_argument("--config", default="C3")
 ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--height", type=int, default=1080)
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--variance", action="store_true", help="the variance mode (rt_variance_set) for every stage timed")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "temporal_bench_C3.jsonl"), help="'' = do not write")
 a = ap.parse_args()
 
@@ -48,6 +49,8 @@ r = Renderer(0)
 r.set_scene_soa(sd.soa, sd.nodes)
 r.set_env(*cf.load_env())
 r.resize(W, H)
+if a.variance:
+    r.set_variance(True)
 cam = ia.Camera(W / H)
 
 
@@ -85,7 +88,7 @@ def chain(k, moving):
     r.denoise_async(views[k & 1] if moving else fp, frame_ptr=out, reuse_guides=True)
 
 
-res = {"config": a.config, "width": W, "height": H, "reps": a.reps}
+res = {"config": a.config, "width": W, "height": H, "reps": a.reps, "variance": a.variance}
 r.temporal_async(fp, advance=True)  # guides and a first output
 res["temporal_advance_reuse_ms"] = timed(lambda k: r.temporal_async(fp, advance=True, reuse_guides=True))
 res["temporal_reuse_ms"] = timed(lambda k: r.temporal_async(fp, reuse_guides=True))
