@@ -174,6 +174,9 @@ const char* rt_last_error(const rt_ctx* ctx);
 /* Device properties used for the launch geometry (CUs, clock). */
 int rt_device_info(const rt_ctx* ctx, int32_t* n_cus, int32_t* blocks_per_cu, int32_t* lds_bytes_per_block);
 
+/* A tree in which some child's box does not lie inside its parent's (aa >= and bb <= per axis; the root's
+ * own box is not looked at) is traversed as the reference traverses it, on the binary tree with the
+ * caller's boxes and without culling: the same results, more slowly. */
 int rt_set_scene(rt_ctx* ctx, const rt_scene_soa* scene);
 int rt_set_scene_encoded(rt_ctx* ctx, const float* tri_enc, int32_t n_triangles, const float* node_enc,
                          int32_t n_nodes);

@@ -94,7 +94,8 @@ SCN_HD inline void geometric_normal(const float* p1, const float* p2, const floa
 //   + the triangle's vertices off the plane (p1, N): max_k |(pk - p1).N|,
 // so t >= t0 - eps * max|1/d_a|.  Returned per scene: K (units of u R) and off; the render
 // doubles eps = K u R + off as safety.  Degenerate (zero-area with a finite fp32 normal) or badly
-// conditioned triangles, or triangles outside their leaf box, give K = inf: no culling.
+// conditioned triangles, triangles outside their leaf box, or a caller's box that does not lie
+// inside its parent's (compile()), give K = inf: no culling.
 struct CullStats {
   double R = 0.0, K = 0.0, off = 0.0;
 };
@@ -160,7 +161,9 @@ inline void pack_material(const rt_material& m, float* o) {
 // below it.  The slab arithmetic is monotone in the box planes, so a box can only be hit when
 // every box above it is: the traversal reaches exactly the leaves whose own box the reference's
 // ray hits, whatever the internal levels are (the reference's exact-tie order is kept separately,
-// by the leaf ranks of its own tree).  The reference's top levels are X-median splits (R18: SAH
+// by the leaf ranks of its own tree).  The reference reaches those same leaves only if each of
+// the caller's tested boxes lies inside its parent's; compile() checks that and keeps a tree
+// that does not nest on the binary traversal.  The reference's top levels are X-median splits (R18: SAH
 // costs above INF = 114514 fall back to the median), so a full-sweep SAH over the leaf boxes
 // (centroid order per axis, cost = area x triangles) gives a tree with fewer node visits.
 // Returns the root of `out` (binary nodes, host only: the device keeps the reference tree).
@@ -261,9 +264,11 @@ inline int rebuild_over_leaves(const std::vector<BNode>& gn, int root, std::vect
 //   A (grand)child box can only be hit when every box above it is (children are min/max over
 //   subsets, and the slab arithmetic is monotone), so the 4-wide traversal reaches exactly the
 //   reference's leaves.
-// Returns false (binary traversal only) when a triangle belongs to two leaves.
+// Returns false (binary traversal only) when a triangle belongs to two leaves, or when the caller's
+// boxes do not nest (`nested` false, compile()): the premise above is then gone.  The leaf ranks
+// are written either way.
 inline bool build_wide(const Options& opt, std::vector<BNode>& gn, int root, std::vector<float>& trin,
-                       std::vector<WNode>& qn, int& qroot, int& qdepth) {
+                       std::vector<WNode>& qn, int& qroot, int& qdepth, bool nested = true) {
   const int nt = (int)(trin.size() / 12);
   std::vector<int> tri_rank(nt, -1);
   int rank = 0;
@@ -283,7 +288,7 @@ inline bool build_wide(const Options& opt, std::vector<BNode>& gn, int root, std
   };
   rank_dfs(root);
   for (int t = 0; t < nt; t++) memcpy(&trin[4 * (3 * (size_t)t + 1) + 3], &tri_rank[t], 4);
-  if (!ok) return false;
+  if (!ok || !nested) return false;
   // The tree that gets collapsed: by default internal levels rebuilt over the reference's leaves
   // (rebuild_over_leaves), Options::rebuild = false keeps the reference's own internal nodes.
   std::vector<BNode> rebuilt;
@@ -477,6 +482,7 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
   for (int m = 0; m < s->n_materials; m++) pack_material(s->materials[m], &c.mats[32 * m]);
   c.tri_mat.assign(s->material_id, s->material_id + nt);
   // ---- BVH: reference numbering -> children-in-parent nodes
+  bool nested = true;  // every child's box lies inside its parent's
   if (nt > 0 && s->n_nodes > 1) {
     if (!s->node_left || !s->node_right || !s->node_n || !s->node_index || !s->node_aa || !s->node_bb)
       return fail(RT_ERR_ARG, "missing node arrays");
@@ -515,6 +521,13 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
       int l = s->node_left[i], r = s->node_right[i];
       const float* la = s->node_aa + 3 * l; const float* lb = s->node_bb + 3 * l;
       const float* ra = s->node_aa + 3 * r; const float* rb = s->node_bb + 3 * r;
+      // Every tested box inside its parent's (a NaN fails; the root's own box is never tested,
+      // RT:338-392): what rebuild_over_leaves, build_wide and the culling bound rest on.
+      if (i != 1)
+        for (int a = 0; a < 3; a++) {
+          const float pa = s->node_aa[3 * i + a], pb = s->node_bb[3 * i + a];
+          if (!(la[a] >= pa && lb[a] <= pb && ra[a] >= pa && rb[a] <= pb)) nested = false;
+        }
       int lr, rr;
       int rc;
       if (is_leaf(l)) { if ((rc = leaf_of(l, lr))) return rc; } else lr = internal_id[l];
@@ -531,7 +544,7 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
     c.has_scene = 1;
   }
   c.qroot = c.root;
-  if (c.has_scene) c.wide = c.qbuilt = build_wide(opt, c.nodes, c.root, c.trin, c.qnodes, c.qroot, c.qdepth);
+  if (c.has_scene) c.wide = c.qbuilt = build_wide(opt, c.nodes, c.root, c.trin, c.qnodes, c.qroot, c.qdepth, nested);
   if (!opt.wide) c.wide = false;
   if (c.nodes.empty()) c.nodes.push_back(BNode{});
   if (c.qnodes.empty()) c.qnodes.push_back(WNode{});
@@ -546,7 +559,7 @@ inline int compile(const rt_scene_soa* s, const Options& opt, Compiled& out, std
   for (size_t i = 0; i < (size_t)nt; i++) hit_record(&c.tri[12 * i], &c.trin[12 * i], &c.hrec[32 * i]);
   {
     const CullStats cs = cull_bound_stats(s);
-    c.cull_R = cs.R; c.cull_K = cs.K; c.cull_off = cs.off;
+    c.cull_R = cs.R; c.cull_K = nested ? cs.K : (double)INFINITY; c.cull_off = cs.off;
   }
   out = std::move(c);
   return RT_OK;
