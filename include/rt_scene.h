@@ -104,7 +104,16 @@ int rts_scene_post_bvh_index(const rts_scene* s, int32_t* pre_to_post);
 
 /* ---- environment -------------------------------------------------------------- */
 /* Radiance .hdr -> float RGB, rows in file order (top row first). *out_rgb allocated with
- * malloc; release with rts_free. */
+ * malloc; release with rts_free.  New-style RLE, flat and old-style run-length scanlines (1,1,1,n
+ * repeat markers) decode as in the reference, and so does a file that ends inside a scanline:
+ * RTS_OK, the rows before it decoded and the rest 0.  RTS_ERR_FORMAT, with *out_rgb NULL and
+ * nothing allocated: no "#?RADIANCE" magic, no empty line ending the header, a resolution line
+ * that is not "-Y h +X w" with w, h > 0, and an old-style run (a marker's count, shifted 8 bits
+ * more for each marker directly before it) longer than the rest of its scanline.  The last one is
+ * where the decoder deliberately departs from the reference, whose oldDecrunch copies such a run
+ * past the end of its scanline buffer (a memory error, not a behaviour to keep).  It also accepts
+ * a header of the magic line alone ("#?RADIANCE\n\n-Y ..."), which the reference does not end at
+ * that empty line (it reads on through the pixels for the next one). */
 int rts_hdr_load(const char* path, int32_t* width, int32_t* height, float** out_rgb);
 /* hdrCache texels (x_sample/W, y_sample/H, pdf) for an RGB float image. */
 int rts_hdr_cache(const float* rgb, int width, int height, float* out_cache);

@@ -999,30 +999,38 @@ struct Reader {
     return d[pos++];
   }
 };
-static bool old_decrunch(unsigned char (*scan)[4], int len, Reader& f) {  // HDRL:161-190
+// A scanline's outcome: decoded, the file ended inside it (the rows before it stand, HDRL:87-88),
+// or an old-style run that does not fit in what is left of the scanline (the reference writes past
+// its buffer there; rts_hdr_load refuses the file).
+enum Scan { SCAN_OK, SCAN_EOF, SCAN_OVERRUN };
+static Scan old_decrunch(unsigned char (*scan)[4], int len, Reader& f) {  // HDRL:161-190
   int rshift = 0;
   while (len > 0) {
     scan[0][0] = (unsigned char)f.getc();
     scan[0][1] = (unsigned char)f.getc();
     scan[0][2] = (unsigned char)f.getc();
     scan[0][3] = (unsigned char)f.getc();
-    if (f.eof) return false;
+    if (f.eof) return SCAN_EOF;
     if (scan[0][0] == 1 && scan[0][1] == 1 && scan[0][2] == 1) {
-      for (int i = scan[0][3] << rshift; i > 0; i--) {
+      // count << rshift in 64 bits: a chain of markers shifts past an int's width (a count of 0
+      // repeats nothing at any shift)
+      const int64_t run = scan[0][3] == 0 ? 0 : rshift > 32 ? INT64_MAX : (int64_t)scan[0][3] << rshift;
+      if (run > len) return SCAN_OVERRUN;
+      for (int i = (int)run; i > 0; i--) {
         memcpy(&scan[0][0], &scan[-1][0], 4);
         scan++;
         len--;
       }
-      rshift += 8;
+      if (rshift <= 32) rshift += 8;
     } else {
       scan++;
       len--;
       rshift = 0;
     }
   }
-  return true;
+  return SCAN_OK;
 }
-static bool decrunch(unsigned char (*scan)[4], int len, Reader& f) {  // HDRL:118-159
+static Scan decrunch(unsigned char (*scan)[4], int len, Reader& f) {  // HDRL:118-159
   if (len < 8 || len > 0x7fff) return old_decrunch(scan, len, f);
   int i = f.getc();
   if (i != 2) {
@@ -1047,10 +1055,10 @@ static bool decrunch(unsigned char (*scan)[4], int len, Reader& f) {  // HDRL:11
       } else {
         while (code-- && j < len) scan[j++][i] = (unsigned char)f.getc();
       }
-      if (f.eof) return false;
+      if (f.eof) return SCAN_EOF;
     }
   }
-  return !f.eof;
+  return f.eof ? SCAN_EOF : SCAN_OK;
 }
 static float convert_component(int expo, int val) {  // HDRL:99-104
   float v = (float)val / 256.0f;
@@ -1072,7 +1080,9 @@ int rts_hdr_load(const char* path, int32_t* width, int32_t* height, float** out_
   Reader f{data.data(), data.size(), 0, false};
   if (data.size() < 11 || memcmp(data.data(), "#?RADIANCE", 10) != 0) return RTS_ERR_FORMAT;
   f.pos = 11;  // fread(10) + fseek(1)
-  int c = 0, oldc;
+  // the skipped byte counts as the line end it is: a header of the magic line alone ends at the
+  // empty line right after it (the reference, starting from 0, reads on into the pixels for one)
+  int c = data[10], oldc;
   while (true) {  // header ends at an empty line
     oldc = c;
     c = f.getc();
@@ -1095,7 +1105,12 @@ int rts_hdr_load(const char* path, int32_t* width, int32_t* height, float** out_
   unsigned char(*scan)[4] = reinterpret_cast<unsigned char(*)[4]>(scanline.data() + 4);  // scan[-1] valid
   float* out = cols;
   for (int y = h - 1; y >= 0; y--) {
-    if (!decrunch(scan, w, f)) break;
+    const Scan sc = decrunch(scan, w, f);
+    if (sc == SCAN_OVERRUN) {
+      free(cols);
+      return RTS_ERR_FORMAT;
+    }
+    if (sc != SCAN_OK) break;
     for (int x = 0; x < w; x++) {  // workOnRGBE HDRL:106-116
       int expo = scan[x][3] - 128;
       out[0] = convert_component(expo, scan[x][0]);

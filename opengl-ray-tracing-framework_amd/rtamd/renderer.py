@@ -492,8 +492,12 @@ class Renderer:
         return d
 
     def set_env(self, hdr: np.ndarray, cache: np.ndarray, hdr_resolution: Optional[int] = None) -> None:
+        """rt_set_env: the map and its sampling cache (scene_lib.hdr_cache), both (h, w, 3).  The
+        library reads w * h * 3 floats from each, so other shapes are refused here."""
         a = np.ascontiguousarray(hdr, np.float32)
         b = np.ascontiguousarray(cache, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3 or b.shape != a.shape:
+            raise ValueError(f"set_env: hdr and cache must both be (h, w, 3), got {a.shape} and {b.shape}")
         h, w, _ = a.shape
         res = w if hdr_resolution is None else hdr_resolution
         self._check(self._L.rt_set_env(self._h, _fp(a), _fp(b), w, h, res), "rt_set_env")
